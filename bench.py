@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Headline benchmark: whole-node records/s scoring a 1000-tree GBDT PMML on MI355X (+ p50 latency).
+"""Headline benchmark: whole-node records/s scoring a 1000-tree GBDT PMML on MI355X (+ p50 latency under ``--full``).
 
 Metric / config from ``BASELINE.json``: "records/sec (whole node) on 1k-tree GBDT PMML at
 1/2/4/8 MI355X; p50 latency" — 1000-tree XGBoost-style GBDT PMML (depth 6, 32 float features),
@@ -29,6 +29,11 @@ RCCL-broadcast to every rank (F2). Rank 0 prints ONE JSON line.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3   # same job, external launcher
     python bench.py --model rf|chain|mlp           # BASELINE configs 3 / 5 / 4
+
+A plain run only sets up, warms up, times ``--steps`` steps and prints the result line.
+``--full`` adds the untimed extras (fp64-oracle spot check, kernel-only throughput, p50/p99
+latency, the CPU rehearsal's gathered-row check); ``--dump-outputs DIR`` writes a seeded sample of
+the last timed step's scores as ``.npy`` files, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -80,10 +85,11 @@ def parse_args(argv=None):
     p.add_argument("--max-inflight", type=int, default=3, help="scored steps in flight before the sink waits")
     p.add_argument("--precision", choices=["fp32", "bf16", "fp8"], default=None,
                    help="default fp32 (trees), bf16 (mlp, BASELINE config 4); fp8 = e4m3 leaves (config 5)")
-    p.add_argument("--latency-batch", type=int, default=4096)
-    p.add_argument("--latency-iters", type=int, default=50)
+    p.add_argument("--latency-batch", type=int, default=4096, help="rows per latency request (only under --full)")
+    p.add_argument("--latency-iters", type=int, default=50, help="timed latency requests (only under --full)")
     p.add_argument("--no-allgather", action="store_true")
-    p.add_argument("--check-rows", type=int, default=8192, help="rows checked against the fp64 oracle (untimed)")
+    p.add_argument("--check-rows", type=int, default=8192,
+                   help="rows checked against the fp64 oracle (untimed; only under --full)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no-numa", action="store_true", help="do not bind to the GPU's NUMA node")
     p.add_argument("--force-dist", action="store_true", help="form a 1-rank RCCL group at N=1 (exercise RCCL)")
@@ -96,7 +102,20 @@ def parse_args(argv=None):
                         "functional rehearsal of N ranks without GPUs -- its numbers are NOT a benchmark")
     p.add_argument("--model-docs", type=int, default=8,
                    help="--models mode: distinct synthetic PMML documents (seeds) the model ids cycle over")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need (each in a run of its own, untimed): the "
+                        "fp64-oracle spot check, the device-resident kernel-only throughput, the p50/p99 latency "
+                        "loop and, under --rehearse-cpu, the per-rank check of every gathered row")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the timed path delivered in its last step -- scores.npy, "
+                        "valid.npy (float32) and row_offsets.npy (float64, source offset of each row) -- to DIR: a "
+                        "fixed seeded sample of at most 2M rows, identical from run to run for the same arguments "
+                        "(with N > 1 ranks every rank's sink then also gathers the row offsets and copies every "
+                        "gathered element to the host: time without it; this is rehearsed over gloo only, the "
+                        "RCCL device path of the sampling has not been run on N > 1 GPUs)")
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     a.trees = a.trees or (500 if a.model == "rf" else 1000)
     a.depth = a.depth or (8 if a.model == "rf" else 6)
     a.features = a.features or (64 if a.model == "mlp" else 32)
@@ -188,15 +207,61 @@ def _write_source_file(args, X, rank):
 class _WaitSink:
     """``--no-allgather`` at N > 1: every rank only waits for its own scored batches."""
 
-    def __init__(self):
+    def __init__(self, on_scored=None):
         self.rows_seen = 0
+        self.on_scored = on_scored
 
     def invoke(self, value) -> None:
-        value[0].wait()
-        self.rows_seen += len(value[0])
+        pb = value[0].wait()
+        self.rows_seen += len(pb)
+        if self.on_scored is not None:
+            self.on_scored(pb.scores, pb.valid, value[1].offset + np.arange(len(pb), dtype=np.int64))
 
     def finish(self) -> None:
         pass
+
+
+DUMP_ROWS = 1 << 21  # sampled rows per dump: 2M x (fp32 score + fp32 valid + fp64 offset) = 32 MB
+
+
+class _OutputSampler:
+    """``--dump-outputs``: keeps a fixed, seeded sample of what the sink received in the last timed
+    step. ``take(scores, valid, offsets)`` is the sink's per-element callback (``on_gathered``): the
+    rows of ``world`` ranks, rank-major, each rank's rows at consecutive source offsets. Only
+    elements of the last step are looked at, and only the sampled rows are copied (the score arrays
+    are views of pinned buffers that later batches overwrite)."""
+
+    def __init__(self, args, world, last_pass_only=False):
+        rows_per_step = args.rows * args.passes
+        self.world = world
+        self.first = (args.warmup + args.steps - 1) * rows_per_step  # source offset of the last step's first row
+        k = max(1, min(rows_per_step, DUMP_ROWS // world))
+        stride = rows_per_step // k
+        # one row out of every ``stride`` consecutive ones (stratified): sorted, distinct, seeded
+        jitter = np.random.default_rng(args.seed + 4242).integers(0, stride, k) if stride > 1 else 0
+        self.pos = np.arange(k, dtype=np.int64) * stride + jitter
+        if last_pass_only:  # ``--api engine``: every pass overwrites the same arrays, only the last one is left
+            self.pos = self.pos[self.pos >= rows_per_step - args.rows]
+        self.parts = []
+
+    def take(self, s, v, o) -> None:
+        assert len(s) == len(o) and len(s) % self.world == 0, (len(s), len(o), self.world)
+        m = len(s) // self.world
+        for r in range(self.world):
+            lo = int(o[r * m]) - self.first if m else -1
+            if lo < 0:
+                continue
+            assert int(o[r * m + m - 1]) - int(o[r * m]) == m - 1, "a rank's rows are not at consecutive offsets"
+            a, b = np.searchsorted(self.pos, [lo, lo + m])
+            idx = r * m + (self.pos[a:b] - lo)
+            self.parts.append((np.asarray(s)[idx].astype(np.float32), np.asarray(v)[idx].astype(np.float32),
+                               (self.first + self.pos[a:b]).astype(np.float64)))
+
+    def write(self, d) -> None:
+        os.makedirs(d, exist_ok=True)
+        for i, name in enumerate(("scores", "valid", "row_offsets")):
+            a = np.concatenate([p[i] for p in self.parts]) if self.parts else np.zeros(0)
+            np.save(os.path.join(d, name + ".npy"), a.astype(np.float64 if i == 2 else np.float32))
 
 
 def _h2d_streams(pipe, args):
@@ -402,9 +467,9 @@ def main(argv=None) -> int:
     model = lm.model
     plan = getattr(model.scorer, "plan", None)
 
-    # ---- untimed correctness spot-check against the float64 oracle (rank 0)
+    # ---- --full: untimed correctness spot-check against the float64 oracle (rank 0)
     check = {}
-    if ctx.rank == 0 and args.check_rows > 0:
+    if args.full and ctx.rank == 0 and args.check_rows > 0:
         compiled = CompiledPmml.from_string(open(path).read())
         Xc = stream_matrix(args.check_rows, args.features, seed=99, missing_rate=0.02)
         s_ref, v_ref = compiled.score_matrix_oracle(Xc)
@@ -435,6 +500,13 @@ def main(argv=None) -> int:
     pipe = None
     job = {}
     rows_per_step = args.rows * args.passes
+    # --dump-outputs: a sample of what the sink receives in the last timed step. Every rank samples,
+    # so that all ranks' sinks post the same collectives; rank 0 alone writes the files
+    sampler = None
+    if args.dump_outputs:
+        engine = args.api == "engine"
+        sampler = _OutputSampler(args, N if gather and not engine else 1, last_pass_only=engine)
+    take = sampler.take if sampler is not None else None
     if args.api == "dsl":
         from flink_jpmml_amd.parallel.sinks import GatherSink
         from flink_jpmml_amd.stream import StreamExecutionEnvironment
@@ -447,7 +519,10 @@ def main(argv=None) -> int:
         env = StreamExecutionEnvironment(config=cfg, dist_ctx=ctx if ctx.is_distributed else None)
         # the library F5 sink: waits for every scored batch; with N > 1 all-gathers the device
         # mirrors over RCCL on its comm stream, overlapping the next batch
-        sink = GatherSink(to="all", lockstep=True, keep=cpu) if gather or not ctx.is_distributed else _WaitSink()
+        if gather or not ctx.is_distributed:
+            sink = GatherSink(to="all", lockstep=True, keep=cpu and args.full, on_gathered=take)
+        else:
+            sink = _WaitSink(take)
         op_cfg = cfg.replace(device_mirror=gather)
         model_ids = None
         if args.models > 1:
@@ -497,7 +572,7 @@ def main(argv=None) -> int:
         seen = sink.rows_seen
         assert seen == (args.warmup + args.steps) * rows_per_step, (seen, rows_per_step)
         assert res.records_in == seen + (args.models if args.models > 1 else 0)  # + the AddMessages
-        if cpu and gather:
+        if cpu and gather and args.full:
             # rehearsal: every rank checks ITS rows inside every gathered element against its own
             # oracle (row order via the source offsets), then the verdicts are all-gathered
             from flink_jpmml_amd.parallel.dist import all_gather_object
@@ -510,7 +585,7 @@ def main(argv=None) -> int:
         pipe = getattr(getattr(op, "inner", op), "_pipeline", None)
         if args.models > 1:
             job["models_served"] = len(op.serving_models)
-            if ctx.rank == 0 and args.check_rows > 0:  # untimed: every model's rows vs its fp64 oracle
+            if args.full and ctx.rank == 0 and args.check_rows > 0:  # untimed: every model's rows vs its fp64 oracle
                 from flink_jpmml_amd.api.batch import RecordBatch as _RB
 
                 Xc = stream_matrix(args.check_rows, args.features, seed=99, missing_rate=0.02)
@@ -547,32 +622,38 @@ def main(argv=None) -> int:
         scorer.wait(h)
         barrier_sync()
         elapsed = time.perf_counter() - t0
+        if sampler is not None:  # the pinned arrays hold the last pass of the last step
+            last_pass = sampler.first + (args.passes - 1) * args.rows
+            sampler.take(score_h.numpy(), valid_h.numpy(), last_pass + np.arange(args.rows, dtype=np.int64))
     if ctx.is_distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if device is not None else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     records_per_s = N * rows_per_step * args.steps / elapsed
+    if sampler is not None and ctx.rank == 0:
+        sampler.write(args.dump_outputs)
 
-    # ---- device-resident kernel throughput (records already in HBM) — reported separately
     n_k = min(args.rows, 1 << 22)
-    kernel_ms = float("nan")
-    if not cpu:
-        kernel_ms = _kernel_ms(plan, X[:n_k], device)
+    kernel_ms = p50 = p99 = None
+    if args.full:
+        # ---- device-resident kernel throughput (records already in HBM) — reported separately
+        if not cpu:
+            kernel_ms = _kernel_ms(plan, X[:n_k], device)
 
-    # ---- p50 latency: one small RecordBatch through model.predict (host records -> host scores)
-    from flink_jpmml_amd.api.batch import RecordBatch
+        # ---- p50 latency: one small RecordBatch through model.predict (host records -> host scores)
+        from flink_jpmml_amd.api.batch import RecordBatch
 
-    Xl = torch.from_numpy(stream_matrix(args.latency_batch, args.features, seed=7))
-    Xl = RecordBatch(Xl if cpu else Xl.pin_memory())
-    lats = []
-    for i in range(args.latency_iters + 5):
-        t1 = time.perf_counter()
-        model.predict(Xl).wait()
-        if i >= 5:
-            lats.append((time.perf_counter() - t1) * 1e3)
-    p50 = float(np.percentile(lats, 50))
-    p99 = float(np.percentile(lats, 99))
+        Xl = torch.from_numpy(stream_matrix(args.latency_batch, args.features, seed=7))
+        Xl = RecordBatch(Xl if cpu else Xl.pin_memory())
+        lats = []
+        for i in range(args.latency_iters + 5):
+            t1 = time.perf_counter()
+            model.predict(Xl).wait()
+            if i >= 5:
+                lats.append((time.perf_counter() - t1) * 1e3)
+        p50 = float(np.percentile(lats, 50))
+        p99 = float(np.percentile(lats, 99))
 
     if ctx.rank == 0:
         default = args.model == "gbdt" and args.source == "synthetic" and args.models == 1
@@ -624,8 +705,8 @@ def main(argv=None) -> int:
             "p50_latency_ms": p50,
             "p99_latency_ms": p99,
             "latency_batch_rows": args.latency_batch,
-            "kernel_only_records_per_s_per_gpu": None if cpu else n_k / (kernel_ms / 1e3),
-            "kernel_ms_per_1M_rows": None if cpu else kernel_ms * (1 << 20) / n_k,
+            "kernel_only_records_per_s_per_gpu": None if kernel_ms is None else n_k / (kernel_ms / 1e3),
+            "kernel_ms_per_1M_rows": None if kernel_ms is None else kernel_ms * (1 << 20) / n_k,
             "h2d_gbps_effective": rows_per_step * args.features * 4 * args.steps / elapsed / 1e9,
             "job": job,
             "model_load_broadcast_s": load_s,
@@ -634,6 +715,8 @@ def main(argv=None) -> int:
                      "chunk_trees": getattr(plan, "chunk_trees", None), "kind": getattr(plan, "kind", None)},
             "check": check,
             "rehearsal_cpu": cpu,
+            "full": bool(args.full),
+            "dump_outputs": args.dump_outputs,
             "metrics": {k: v for k, v in METRICS.summary()["counters"].items() if not k.startswith("model_cache")},
         }
         print(json.dumps(out), flush=True)

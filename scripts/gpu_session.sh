@@ -30,11 +30,11 @@ for s in $STEPS; do
   case $s in
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -v -x -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps "${BENCH_STEPS:-20}" --warmup 3 ;;
+    bench) run bench 600 python bench.py --steps "${BENCH_STEPS:-20}" --warmup 3 --full ;;
     prof)
       mkdir -p "$OUT/prof"
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" \
-          -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --latency-iters 5 \
+          -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --full --latency-iters 5 \
           > "$OUT/prof.log" 2>&1 ); rc=$?
       echo "=== prof rc=$rc" | tee -a "$OUT/session.log"
       if fatal $rc; then exit $rc; fi ;;
@@ -53,7 +53,7 @@ for s in $STEPS; do
       mkdir -p "$OUT/trace"
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats \
           -d "$OUT/trace" -o trace --output-format csv -- python3 "$ROOT/bench.py" --steps 4 --warmup 1 \
-          --latency-iters 3 --check-rows 0 > "$OUT/trace.log" 2>&1 ); rc=$?
+          --full --latency-iters 3 --check-rows 0 > "$OUT/trace.log" 2>&1 ); rc=$?
       echo "=== trace rc=$rc" | tee -a "$OUT/session.log"
       if fatal $rc; then exit $rc; fi ;;
     *) echo "unknown step $s" ;;

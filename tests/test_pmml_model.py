@@ -217,14 +217,19 @@ def test_no_target_is_empty(fixtures_dir):
     assert m.predict(DenseVector(1, 1, 1, 1)) == Prediction(EmptyScore)
 
 
-REF = "/root/reference/flink-jpmml-assets/src/main/resources"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pmml")
+REF_FILES = ["kmeans.xml", "kmeans32.xml", "kmeans40.xml", "kmeans41.xml", "kmeans42.xml", "kmeans_empty.xml",
+             "kmeans_nooutput.xml", "kmeans_nooutput_notarget.xml", "kmeans_stringfields.xml"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not mounted")
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(REF, "*.xml"))))
-def test_reference_fixture_files(path):
-    """Parse the reference's own PMML assets (read-only, data files) and check the goldens."""
-    name = os.path.basename(path)
+def test_reference_fixture_set_is_complete():
+    assert sorted(os.path.basename(p) for p in glob.glob(os.path.join(REF, "*.xml"))) == REF_FILES
+
+
+@pytest.mark.parametrize("name", REF_FILES)
+def test_reference_fixture_files(name):
+    """Parse the reference's own PMML assets (data files, stored under ``tests/golden``) and check the goldens."""
+    path = os.path.join(REF, name)
     if name == "kmeans_empty.xml":
         with pytest.raises(PmmlParseError):
             PmmlModel.from_path(path)
