@@ -64,7 +64,7 @@ __device__ __forceinline__ float prep_value(float x, const FieldPrep& p, bool* b
     if (fl & FP_HAS_INTERVAL) {
       bool lo_ok = (fl & FP_LO_OPEN) ? (x > p.lo) : (x >= p.lo);
       bool hi_ok = (fl & FP_HI_OPEN) ? (x < p.hi) : (x <= p.hi);
-      invalid = !(lo_ok && hi_ok);
+      invalid = invalid || !(lo_ok && hi_ok);
     }
     if (fl & FP_CODE_RANGE) invalid = invalid || !(x >= 0.f && x < p.hi);
     if (fl & FP_INTEGER) invalid = invalid || (floorf(x) != x);

@@ -472,7 +472,11 @@ def fold_splits(f, ops: np.ndarray, ts: np.ndarray) -> tuple:
     """Rewrite splits ``f(x) OP t`` (OP codes of models/tree.py) on a monotone ``f`` into
     ``x < C`` (OP_LT) or ``x >= C`` (OP_GE) with fp32 ``C``, exact for every finite fp32 x: ``P(x)
     = f(x) OP t`` is monotone in x, so the cut is found by bisecting the ordered fp32 keys (33
-    steps) with the oracle's ``f`` — vectorised over all splits of one field."""
+    steps) with the oracle's ``f`` — vectorised over all splits of one field. A predicate that is
+    constant over the finite line keeps that value at ``x = ±inf`` too (``x >= -inf`` / ``x <
+    -inf``); a predicate with a finite cut is exact at ``±inf`` when ``f`` is monotone there as
+    well (it is for the affine and ``NormContinuous`` shapes that fold). NaN never reaches the
+    comparison's answer: a missing value takes the node's default direction."""
     from ..models.tree import OP_GE, OP_GT, OP_LE, OP_LT
 
     ops = np.asarray(ops)
@@ -499,9 +503,10 @@ def fold_splits(f, ops: np.ndarray, ts: np.ndarray) -> tuple:
         lo = np.where(active & below & (hi - lo > 1), mid, lo)
         hi = np.where(active & ~below & (hi - lo > 1), mid, hi)
     cut = _f32_from_key(hi)
-    new_ops = np.where(rising, OP_GE, OP_LT).astype(ops.dtype)
-    # constant predicates: always true -> x < +inf, always false -> x < -inf
-    new_t = np.where(active, cut, np.where(p_lo, np.inf, -np.inf))
+    # constant predicates: always true -> x >= -inf (x < +inf would be false at x = +inf, a value
+    # the oracle accepts), always false -> x < -inf
+    new_ops = np.where(rising | (~active & p_lo), OP_GE, OP_LT).astype(ops.dtype)
+    new_t = np.where(active, cut, -np.inf)
     return new_ops, new_t
 
 

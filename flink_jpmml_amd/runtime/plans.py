@@ -8,8 +8,10 @@ table) and exposes
 * :meth:`DevicePlan.score` — convenience host/device entry point.
 
 Numerics: inputs are fp32 on the device. Every fp64 constant that is compared against an input
-(split thresholds, validity intervals) is rounded *directionally* to fp32 so the fp32 comparison
-gives exactly the fp64 answer for any fp32 input (``_ceil32``/``_floor32``/``_next_up``).
+(split thresholds, validity intervals of every dataType, ``asMissingValues`` outlier bounds) is
+rounded *directionally* to fp32 so the fp32 comparison gives exactly the fp64 answer for any fp32
+input (``_ceil32``/``_floor32``/``_next_up``); ``tests/test_boundary_inputs.py`` holds every one of
+them to that at the constant +-2 ulps. A double input fp32 cannot hold is rounded to nearest first.
 Accumulations (tree sums, dot products) run in fp32; the parity tolerance against the float64
 oracle is documented per test.
 """
@@ -170,20 +172,14 @@ def build_field_prep(compiled, fields: List[str]) -> Tuple[np.ndarray, bool]:
                 constrained = True
                 lo_open = not iv.closure.startswith("closed")
                 hi_open = not iv.closure.endswith("Closed")
-                if df.data_type == "float":
-                    # fp32 inputs: directional rounding makes the fp32 test exact
-                    if iv.left is not None:
-                        lo = _floor32(iv.left) if lo_open else _ceil32(iv.left)
-                    if iv.right is not None:
-                        hi = _ceil32(iv.right) if hi_open else _floor32(iv.right)
-                else:
-                    # fp64 inputs arrive rounded-to-nearest: rounding the bounds the same way keeps
-                    # every valid value valid (monotonic rounding); only values within half an
-                    # fp32 ulp outside a bound can be misclassified
-                    if iv.left is not None:
-                        lo = float(np.float32(iv.left))
-                    if iv.right is not None:
-                        hi = float(np.float32(iv.right))
+                # the device compares fp32 inputs: directional rounding makes the fp32 test give the
+                # fp64 answer for every fp32 x, whatever the field's dataType. (A double input that
+                # fp32 cannot hold arrives rounded to nearest and is classified as that fp32 value:
+                # within half an fp32 ulp of a bound it can differ from the fp64 oracle.)
+                if iv.left is not None:
+                    lo = _floor32(iv.left) if lo_open else _ceil32(iv.left)
+                if iv.right is not None:
+                    hi = _ceil32(iv.right) if hi_open else _floor32(iv.right)
                 fl |= (FP_LO_OPEN if lo_open else 0) | (FP_HI_OPEN if hi_open else 0)
             elif df.values and df.is_string:
                 fl |= FP_CODE_RANGE
@@ -226,10 +222,13 @@ def build_field_prep(compiled, fields: List[str]) -> Tuple[np.ndarray, bool]:
                     irepl = schema.lookup(name, mf.invalid_value_replacement)
             if optype == "continuous" and mf.outliers in ("asMissingValues", "asExtremeValues"):
                 fl |= FP_OUTLIER_AS_MISSING if mf.outliers == "asMissingValues" else FP_OUTLIER_AS_EXTREME
+                # asMissingValues compares (x < low, x > high): directional rounding keeps the fp32
+                # test exact; asExtremeValues clamps, and the clamped value must be fp32(bound)
+                as_missing = mf.outliers == "asMissingValues"
                 if mf.low_value is not None:
-                    out_lo = mf.low_value
+                    out_lo = _ceil32(mf.low_value) if as_missing else mf.low_value
                 if mf.high_value is not None:
-                    out_hi = mf.high_value
+                    out_hi = _floor32(mf.high_value) if as_missing else mf.high_value
             if mf.missing_value_replacement is not None:
                 fl |= FP_HAS_MISSING_REPL
                 mrepl = schema.lookup(name, mf.missing_value_replacement)
