@@ -13,6 +13,7 @@ from .api import (  # noqa: E402
     DenseVector,
     ModelReader,
     PmmlModel,
+    SparseRecordBatch,
     SparseVector,
 )
 from .domain import (  # noqa: E402
@@ -29,5 +30,5 @@ from .domain import (  # noqa: E402
 
 __all__ = [
     "AddMessage", "DelMessage", "DenseVector", "EmptyScore", "ModelId", "ModelInfo", "ModelReader",
-    "PmmlModel", "Prediction", "Score", "ServingMessage", "SparseVector", "Target", "__version__",
+    "PmmlModel", "Prediction", "Score", "ServingMessage", "SparseRecordBatch", "SparseVector", "Target", "__version__",
 ]

@@ -15,6 +15,7 @@ from .exceptions import (
     UnsupportedFeatureException,
     WrongModelIdFormat,
 )
+from .batch import PredictionBatch, RecordBatch, SparseRecordBatch
 from .managers import MetadataManager, ModelsManager, metadata_manager, models_manager
 from .pipeline import FieldValue
 from .pmml_model import PmmlModel
@@ -25,7 +26,8 @@ __all__ = [
     "DenseVector", "EMPTY_EVALUATOR", "EmptyEvaluator", "EmptyEvaluatorException", "EvaluationException",
     "Evaluator", "FieldValue", "FsReader", "InputPreparationException", "InputValidationException",
     "JPMMLExtractionException", "MetadataManager", "ModelLoadingException", "ModelReader", "ModelsManager",
-    "NoSuchElementException", "PmmlEvaluator", "PmmlInput", "PmmlModel", "PmmlParseError", "SparseVector",
+    "NoSuchElementException", "PmmlEvaluator", "PmmlInput", "PmmlModel", "PmmlParseError", "PredictionBatch",
+    "RecordBatch", "SparseRecordBatch", "SparseVector",
     "UnsupportedFeatureException", "Vector", "WrongModelIdFormat", "metadata_manager", "models_manager",
     "pack_vectors", "vector_conversion",
 ]

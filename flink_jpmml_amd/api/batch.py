@@ -15,6 +15,10 @@ someone reads ``.scores`` / ``.valid``, iterates, or indexes it; ``Prediction`` 
 built when a consumer asks for one (``batch[i]``, iteration, :meth:`PredictionBatch.to_list`).
 ``PredictionBatch[i] == model.predict(batch.vector(i))`` for every row — the per-record contract
 of the reference holds row by row.
+
+Wide, mostly-absent records travel as a :class:`SparseRecordBatch` (CSR): a RecordBatch subclass
+whose stored entries alone cross PCIe and are expanded on the device; everywhere else it densifies
+lazily and behaves like the dense batch of the same vectors.
 """
 
 from __future__ import annotations
@@ -259,6 +263,216 @@ class RecordBatch:
         return f"RecordBatch(rows={len(self)}, features={self.n_features}{mid})"
 
 
+def _host_array(a: Any, dtype) -> np.ndarray:
+    """1-D contiguous host array of ``dtype`` over ``a`` (a view where ``a`` already is one; a
+    host torch tensor is viewed, not copied)."""
+    if hasattr(a, "detach") and hasattr(a, "numpy"):
+        a = a.detach().numpy()
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+
+class SparseRecordBatch(RecordBatch):
+    """``rows × width`` records in CSR form: row ``i`` stores ``values[indptr[i]:indptr[i+1]]`` at
+    the columns ``indices[indptr[i]:indptr[i+1]]``; every other entry is *absent* (PMML missing,
+    or ``replace_nan``). A NaN *stored* in ``values`` stays a missing value, as per record.
+
+    * ``indptr`` — ``[n+1]`` int32 or int64, ``indices`` — int32, ``values`` — float32: host numpy
+      arrays (views of the pinned tensors for batches from :meth:`pinned` / :meth:`to_pinned`).
+      ``indices`` / ``values`` may be longer than ``indptr[-1]`` only in a :meth:`pinned` batch.
+
+    The device scorer ships the three arrays and expands them on the GPU
+    (``ops/csrc/sparse.hip``). Every consumer that knows nothing about CSR reads ``X`` /
+    ``absent``, which densify on the host on first use (counted in
+    ``scoring.sparse_densified_host``) and then behave like a :class:`RecordBatch`'s.
+    Per-row ``model_ids`` are not supported on sparse batches."""
+
+    __slots__ = ("indptr", "indices", "values", "width", "_X", "_absent", "_pinned")
+
+    def __init__(self, indptr: Any, indices: Any, values: Any, width: int, model_id: Optional[str] = None,
+                 payload: Optional[Sequence[Any]] = None, offset: int = 0, model_ids: Any = None,
+                 validated: bool = False):
+        tensors = (indptr, indices, values)
+        ip = indptr.detach().numpy() if hasattr(indptr, "detach") else np.asarray(indptr)
+        if ip.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            ip = ip.astype(np.int64)
+        self.indptr = np.ascontiguousarray(ip).reshape(-1)
+        if self.indptr.size < 1:
+            raise ValueError("SparseRecordBatch.indptr needs at least one entry ([n+1] row starts)")
+        self.indices = _host_array(indices, np.int32)
+        self.values = _host_array(values, np.float32)
+        self.width = int(width)
+        if self.width < 0:
+            raise ValueError(f"SparseRecordBatch.width must not be negative, got {self.width}")
+        # the caller's pinned tensors, when the arrays above are views of them (no staging copy then)
+        self._pinned = tensors if all(hasattr(t, "is_pinned") and t.is_pinned() for t in tensors) and all(
+            v.ctypes.data == t.data_ptr() for v, t in zip((self.indptr, self.indices, self.values), tensors)) else None
+        # the base fields (and its row-count checks, through __len__); X / absent stay unset: lazy
+        super().__init__(None, model_id=model_id, model_ids=model_ids, payload=payload, offset=offset)
+        if not validated:
+            self.validate()
+
+    def validate(self) -> "SparseRecordBatch":
+        """Check the CSR invariants (vectorised); ``ValueError`` on the first one broken."""
+        ip, idx, width = self.indptr, self.indices, self.width
+        if int(ip[0]) != 0:
+            raise ValueError(f"SparseRecordBatch: indptr[0] must be 0, got {int(ip[0])}")
+        counts = np.diff(ip)
+        if counts.size and counts.min() < 0:
+            raise ValueError("SparseRecordBatch: indptr must be non-decreasing")
+        if not int(ip[-1]) == idx.size == self.values.size:
+            raise ValueError(f"SparseRecordBatch: indptr[-1]={int(ip[-1])}, {idx.size} indices and "
+                             f"{self.values.size} values must agree")
+        if idx.size:
+            if idx.min() < 0 or idx.max() >= width:
+                raise ValueError(f"SparseRecordBatch: indices must satisfy 0 <= index < width ({width})")
+            step_ok = idx[1:] > idx[:-1]
+            starts = ip[1:-1][(ip[1:-1] > 0) & (ip[1:-1] < idx.size)]
+            step_ok[starts - 1] = True  # the first entry of a row follows another row's last
+            if not step_ok.all():
+                raise ValueError("SparseRecordBatch: indices must be strictly increasing within each row")
+        return self
+
+    # ------------------------------------------------------------------ construction
+    @staticmethod
+    def from_vectors(vectors: Sequence[Any], width: int, model_id: Optional[str] = None,
+                     payload: Optional[Sequence[Any]] = None, offset: int = 0) -> "SparseRecordBatch":
+        """The CSR form of Dense/Sparse vectors (:func:`~flink_jpmml_amd.api.vectors.to_csr`): dense
+        vectors store every entry; a vector of the wrong size becomes an empty row reported
+        invalid by :meth:`size_ok`, as in :meth:`RecordBatch.from_vectors`."""
+        from .vectors import _to_csr
+
+        vs = vectors if isinstance(vectors, (list, tuple)) else list(vectors)
+        indptr, idx, val, ok = _to_csr(vs, width)
+        # SparseVector sorts and range-checks its indices; only duplicates are left to reject
+        b = SparseRecordBatch(indptr, idx, val, width, model_id=model_id, payload=payload, offset=offset)
+        b._size_ok = None if ok.all() else ok
+        return b
+
+    @staticmethod
+    def from_csr(obj: Any, width: Optional[int] = None, model_id: Optional[str] = None,
+                 payload: Optional[Sequence[Any]] = None, offset: int = 0,
+                 validated: bool = False) -> "SparseRecordBatch":
+        """From anything with ``indptr`` / ``indices`` / ``data`` attributes (a scipy
+        ``csr_matrix``, for one; its ``shape[1]`` is the width unless given)."""
+        if width is None:
+            width = int(obj.shape[1])
+        return SparseRecordBatch(obj.indptr, obj.indices, obj.data, width, model_id=model_id, payload=payload,
+                                 offset=offset, validated=validated)
+
+    @staticmethod
+    def pinned(n: int, nnz_capacity: int, width: int) -> "SparseRecordBatch":
+        """An uninitialised, unvalidated batch in pinned host memory for producers that fill
+        ``indptr`` / ``indices`` / ``values`` in place; ``indptr[-1]`` says how many of the
+        ``nnz_capacity`` entries are in use (:meth:`validate` checks a filled batch whose
+        capacity is exact). Pageable memory on hosts without a GPU."""
+        import torch
+
+        pin = torch.cuda.is_available()
+        return SparseRecordBatch(torch.empty(n + 1, dtype=torch.int32, pin_memory=pin),
+                                 torch.empty(nnz_capacity, dtype=torch.int32, pin_memory=pin),
+                                 torch.empty(nnz_capacity, dtype=torch.float32, pin_memory=pin), width,
+                                 validated=True)
+
+    def to_pinned(self) -> "SparseRecordBatch":
+        """This batch with its three arrays copied into pinned host memory (no-op if pinned)."""
+        import torch
+
+        if self._pinned is not None:
+            return self
+        nnz = self.nnz
+        parts = []
+        for a in (self.indptr, self.indices[:nnz], self.values[:nnz]):
+            src = torch.from_numpy(a)
+            t = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+            t.copy_(src)
+            parts.append(t)
+        b = SparseRecordBatch(*parts, self.width, model_id=self.model_id, payload=self.payload, offset=self.offset,
+                              validated=True)
+        b._size_ok, b.created = self._size_ok, self.created
+        return b
+
+    def to_record_batch(self) -> RecordBatch:
+        """The equivalent dense :class:`RecordBatch` (fp32 ``X``, the "not stored" mask as
+        ``absent``; no mask when nothing is absent and nothing is NaN, as ``from_vectors``)."""
+        X, absent = self.X, self.absent
+        if not absent.any() and not np.isnan(X).any():
+            absent = None
+        b = RecordBatch(X, model_id=self.model_id, absent=absent, payload=self.payload, offset=self.offset)
+        b._size_ok, b.created = self._size_ok, self.created
+        return b
+
+    # ------------------------------------------------------------------ dense fallback (lazy)
+    def _densify(self) -> None:
+        from ..utils.metrics import METRICS
+
+        n, nnz = len(self), self.nnz
+        X = np.full((n, self.width), np.nan, dtype=np.float32)
+        absent = np.ones((n, self.width), dtype=bool)
+        rows = np.repeat(np.arange(n), np.diff(self.indptr))
+        X[rows, self.indices[:nnz]] = self.values[:nnz]
+        absent[rows, self.indices[:nnz]] = False
+        if self._size_ok is not None:  # wrong-size vectors: all-NaN rows with nothing "absent"
+            absent[~self._size_ok] = False
+        self._X, self._absent = X, absent
+        METRICS.inc("scoring.sparse_densified_host")
+
+    @property
+    def X(self) -> np.ndarray:  # type: ignore[override]
+        if self._X is None:
+            self._densify()
+        return self._X
+
+    @X.setter
+    def X(self, value: Any) -> None:
+        self._X = value
+
+    @property
+    def absent(self) -> np.ndarray:  # type: ignore[override]
+        if self._absent is None:
+            self._densify()
+        return self._absent
+
+    @absent.setter
+    def absent(self, value: Any) -> None:
+        self._absent = value
+
+    @property
+    def model_ids(self) -> None:  # type: ignore[override]
+        return None
+
+    @model_ids.setter
+    def model_ids(self, value: Any) -> None:
+        if value is not None:
+            raise ValueError("SparseRecordBatch: per-row model_ids are out of scope for sparse batches "
+                             "(use one model_id per batch, or a dense RecordBatch)")
+        self._ids = self._codes = self._keys = None
+
+    # ------------------------------------------------------------------ access (no densifying)
+    @property
+    def nnz(self) -> int:
+        return int(self.indptr[-1])
+
+    def __len__(self) -> int:
+        return int(self.indptr.size) - 1
+
+    @property
+    def n_features(self) -> int:
+        return self.width
+
+    def vector(self, i: int) -> Vector:
+        """Row ``i`` as the :class:`SparseVector` of its stored entries."""
+        n = len(self)
+        if not -n <= i < n:
+            raise IndexError(f"row {i} of a {n}-row batch")
+        i %= n
+        a, b = int(self.indptr[i]), int(self.indptr[i + 1])
+        return SparseVector(self.width, self.indices[a:b], self.values[a:b].astype(np.float64))
+
+    def __repr__(self) -> str:
+        mid = f", model_id={self.model_id!r}" if self.model_id else ""
+        return f"SparseRecordBatch(rows={len(self)}, features={self.width}, nnz={self.nnz}{mid})"
+
+
 class PredictionBatch:
     """Scores of one RecordBatch, possibly still being computed on the GPU.
 
@@ -434,4 +648,4 @@ def as_record_batch(x: Any, width: Optional[int] = None) -> Optional[RecordBatch
     return None
 
 
-__all__ = ["PredictionBatch", "RecordBatch", "as_record_batch", "as_vector"]
+__all__ = ["PredictionBatch", "RecordBatch", "SparseRecordBatch", "as_record_batch", "as_vector"]

@@ -32,7 +32,7 @@ from .evaluator import EMPTY_EVALUATOR, Evaluator
 from .exceptions import InputValidationException, JPMMLExtractionException
 from .pipeline import FieldValue, Pipeline
 from .reader import ModelReader
-from .batch import PredictionBatch, RecordBatch, as_record_batch
+from .batch import PredictionBatch, RecordBatch, SparseRecordBatch, as_record_batch
 from .vectors import Vector, as_vector, pack_vectors_masked
 
 logger = logging.getLogger(__name__)
@@ -320,13 +320,27 @@ class PmmlModel(Pipeline):
         return compiled.score_matrix(X, replace_nan=replace_nan, device=device, **opts)
 
     def predict_vectors(self, vectors: Sequence[Any], replace_nan: Optional[float] = None, device: Any = None,
-                        **opts) -> List[Prediction]:
-        """Batch version of :meth:`predict` over vector objects → list of :class:`Prediction`."""
+                        sparse: bool = False, **opts) -> List[Prediction]:
+        """Batch version of :meth:`predict` over vector objects → list of :class:`Prediction`.
+        ``sparse=True`` keeps the vectors in CSR form (:class:`SparseRecordBatch`, fp32 values): on
+        a device only the stored entries are shipped and ``pmml_csr_expand`` rebuilds the rows
+        there; on the host the batch densifies as usual. CSR values are fp32, so every route reads
+        the vectors' entries rounded to fp32: on a device that is what ``sparse=False`` reads too;
+        on the host ``sparse=False`` keeps float64, and the two agree exactly only for values fp32
+        holds."""
         compiled = self.evaluator.model
         width = len(compiled.active_fields)
-        X, absent, ok_size = pack_vectors_masked(vectors, width)
-        # replace_nan fills only the entries sparse vectors do not store (per-record parity)
-        scores, valid = compiled.score_matrix(X, replace_nan=replace_nan, device=device, absent=absent, **opts)
+        if sparse:
+            batch = SparseRecordBatch.from_vectors(vectors, width)
+            ok_size = batch.size_ok()
+            if device is None:
+                scores, valid = compiled.score_matrix_oracle(batch.X, replace_nan, batch.absent)
+            else:
+                scores, valid = compiled.plan(device, **opts).score_csr(batch, replace_nan)
+        else:
+            X, absent, ok_size = pack_vectors_masked(vectors, width)
+            # replace_nan fills only the entries sparse vectors do not store (per-record parity)
+            scores, valid = compiled.score_matrix(X, replace_nan=replace_nan, device=device, absent=absent, **opts)
         if not isinstance(scores, np.ndarray):
             scores = scores.detach().cpu().numpy()
             valid = valid.detach().cpu().numpy()

@@ -3,7 +3,8 @@ reference API, `S/api/converter/VectorConverter.scala:58-86`).
 
 Both are light wrappers over numpy arrays. Batches of vectors are packed into one
 ``[rows, size]`` float matrix with ``NaN`` for absent sparse entries by :func:`pack_vectors`
-(host side) or the ``pack_csr`` HIP kernel (device side).
+(host side), or shipped as CSR (:func:`to_csr`) and expanded by the ``pmml_csr_expand`` HIP kernel
+(device side).
 """
 
 from __future__ import annotations
@@ -157,19 +158,34 @@ def _fastpath():
 
 
 def to_csr(vectors: Sequence[VectorLike], width: int):
-    """CSR view ``(indptr int32, indices int32, values float32)`` of a vector batch — the input of the
-    device-side ``pack_csr`` kernel (dense vectors contribute all their entries)."""
-    indptr = np.zeros(len(vectors) + 1, dtype=np.int32)
+    """CSR view ``(indptr int32, indices int32, values float32)`` of a vector batch — what a
+    :class:`~flink_jpmml_amd.api.batch.SparseRecordBatch` holds and the ``pmml_csr_expand`` HIP
+    kernel (``ops/csrc/sparse.hip``) expands on the device. Dense vectors contribute all their
+    entries (a stored NaN included); a vector whose size is not ``width`` contributes an empty
+    row, as its all-NaN row in :func:`pack_vectors_masked`."""
+    return _to_csr(vectors, width)[:3]
+
+
+def _to_csr(vectors: Sequence[VectorLike], width: int):
+    """:func:`to_csr` plus ``ok[i]`` = "vector ``i`` has size ``width``"."""
+    n = len(vectors)
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    ok = np.ones(n, dtype=bool)
     idx_parts, val_parts = [], []
     for i, v in enumerate(vectors):
         v = as_vector(v)
+        if v.size != width:
+            ok[i] = False
+            indptr[i + 1] = indptr[i]
+            continue
         if isinstance(v, SparseVector):
             idx_parts.append(v.indices.astype(np.int32))
-            val_parts.append(v.data.astype(np.float32))
         else:
-            idx_parts.append(np.arange(v.size, dtype=np.int32))
-            val_parts.append(v.data.astype(np.float32))
+            idx_parts.append(np.arange(width, dtype=np.int32))
+        val_parts.append(v.data.astype(np.float32))
         indptr[i + 1] = indptr[i] + idx_parts[-1].size
+    if indptr[-1] > np.iinfo(np.int32).max:
+        raise ValueError(f"to_csr: {int(indptr[-1])} stored entries do not fit an int32 indptr")
     idx = np.concatenate(idx_parts) if idx_parts else np.zeros(0, np.int32)
     val = np.concatenate(val_parts) if val_parts else np.zeros(0, np.float32)
-    return indptr, idx, val
+    return indptr.astype(np.int32), idx, val, ok

@@ -3,7 +3,8 @@
 Kernels (``csrc/``): ``tree.hip`` (perfect / pointer / wide tree-ensemble traversal, split
 reduce), ``cluster.hip`` (center-based clustering), ``linear.hip`` (regression tables + links),
 ``mlp.hip`` (fused all-layer MFMA MLP, bf16 and fp32), ``svm.hip`` (kernel eval + votes),
-``host.hip`` (zero-copy / copy helpers). Shared device code: ``common.h`` (field preparation,
+``sparse.hip`` (CSR record batches expanded into the dense input tile; wrapper and numpy twin in
+``sparse.py``), ``host.hip`` (zero-copy / copy helpers). Shared device code: ``common.h`` (field preparation,
 LDS staging), ``epilogue.h`` (fused target decode).
 """
 

@@ -259,7 +259,14 @@ class DeriveArgs(ctypes.Structure):
                 ("n_insn", c_int), ("n_sel", c_int), ("out", c_void_p), ("row_ok", c_void_p)]
 
 
+class CsrExpandArgs(ctypes.Structure):
+    """sparse.hip CsrExpandArgs: one CSR slice (indptr rebased to 0) -> its dense [m, F] tile."""
+    _fields_ = [("indptr", c_void_p), ("indices", c_void_p), ("values", c_void_p), ("out", c_void_p),
+                ("m", c_int), ("F", c_int), ("nnz", c_int), ("fill", c_float)]
+
+
 _ABI = {
+    "pmml_csr_expand_args_size": CsrExpandArgs,
     "pmml_segment_args_size": SegArgs,
     "pmml_textparse_args_size": TextParseArgs,
     "pmml_derive_args_size": DeriveArgs,
@@ -392,6 +399,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_tree_lds_launch.restype = c_int
         lib.pmml_tree_lds_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
         lib.pmml_tree_lds_bytes.restype = ctypes.c_longlong
+        lib.pmml_csr_expand.argtypes = [c_void_p, ctypes.POINTER(CsrExpandArgs)]
+        lib.pmml_csr_expand.restype = c_int
+        lib.pmml_csr_expand_rows.argtypes = [c_int]
+        lib.pmml_csr_expand_rows.restype = c_int
         _lib = lib
         return lib
 

@@ -15,6 +15,12 @@ only synchronisation points are reading that future and the in-flight cap (backp
 Gen5 (≈50+ GB/s per GPU) is the usual bound for wide fp32 records; the kernels run far below it
 (see ``profiles/``).
 
+A :class:`~flink_jpmml_amd.api.batch.SparseRecordBatch` takes the same ring without being
+densified on the host: each slice's CSR arrays (``indptr`` rebased to 0, ``indices``, ``values``)
+are copied into staging buffers that belong to the ring slot, ``pmml_csr_expand`` rebuilds the dense
+rows in the slot on the compute stream (absent entries take ``replace_nan``, else NaN), and the plan
+runs on them as on any other slot.
+
 One :class:`DevicePipeline` (streams + input ring) is shared by every model an operator serves on
 a device, so a dynamic-serving operator with 64 cached models holds one ring, not 64.
 
@@ -39,7 +45,8 @@ from typing import Tuple, List, Optional
 
 import numpy as np
 
-from ..api.batch import PredictionBatch, RecordBatch
+from ..api.batch import PredictionBatch, RecordBatch, SparseRecordBatch
+from ..ops.sparse import MAX_WIDTH as CSR_MAX_WIDTH
 from ..utils.metrics import METRICS
 from ..utils.profiling import prange
 
@@ -85,6 +92,8 @@ class DevicePipeline:
         self.used = [False] * self.depth
         self.next = 0
         self._dev_ptr_cache = {}
+        # CSR staging of each ring slot (sparse batches): [indptr int32, indices int32, values fp32]
+        self.csr: List = [None] * self.depth
 
     def ensure_slots(self, elems: int) -> None:
         if elems <= self.slot_elems:
@@ -97,6 +106,28 @@ class DevicePipeline:
                 t.record_stream(st)
         self.slots = [torch.empty(elems, dtype=torch.float32, device=self.device) for _ in range(self.depth)]
         self.slot_elems = elems
+
+    def ensure_csr(self, slot: int, rows: int, nnz: int):
+        """The CSR staging tensors of ring slot ``slot`` with room for ``rows + 1`` indptr words and
+        ``nnz`` entries (grown on demand, like :meth:`ensure_slots`). The slot's events order their
+        reuse: the next H2D into them waits for ``ev_comp[slot]``."""
+        import torch
+
+        cur = self.csr[slot]
+        if cur is not None and cur[0].numel() >= rows + 1 and cur[1].numel() >= nnz:
+            return cur
+        if cur is not None:  # queued kernels / copies may still use the old staging
+            for t in cur:
+                t.record_stream(self.comp)
+                for st in self.h2ds:
+                    t.record_stream(st)
+            rows, nnz = max(rows, cur[0].numel() - 1), max(nnz, cur[1].numel())
+        cap = max(1024, nnz + (nnz >> 2))  # headroom: slices of one stream differ in nnz
+        cur = [torch.empty(max(rows, self.B) + 1, dtype=torch.int32, device=self.device),
+               torch.empty(cap, dtype=torch.int32, device=self.device),
+               torch.empty(cap, dtype=torch.float32, device=self.device)]
+        self.csr[slot] = cur
+        return cur
 
     @property
     def h2d_streams_in_use(self) -> Optional[int]:
@@ -170,6 +201,27 @@ def _pin(X):
     out = torch.empty(src.shape, dtype=torch.float32, pin_memory=True)
     out.copy_(src)
     return out
+
+
+def _pin_as(a: np.ndarray, dtype):
+    """1-D host array → pinned tensor of ``dtype`` (one host copy)."""
+    import torch
+
+    src = torch.from_numpy(np.ascontiguousarray(a))
+    out = torch.empty(src.shape, dtype=dtype, pin_memory=True)
+    out.copy_(src)
+    return out
+
+
+@dataclass
+class _CsrSource:
+    """A sparse batch staged for the H2D ring (see :meth:`StreamingScorer._stage_csr`)."""
+    batch: object
+    indptr: np.ndarray  # the batch's own row starts (host)
+    rebased: object  # pinned int32: every micro-batch slice's indptr rebased to 0
+    indices: object  # pinned int32 [>= nnz]
+    values: object  # pinned fp32 [>= nnz]
+    fill: float
 
 
 class StreamingScorer:
@@ -283,6 +335,12 @@ class StreamingScorer:
                 p.ev_h2d[slot][j].record(st)
             for ev in p.ev_h2d[slot][: len(h2ds)]:
                 p.comp.wait_event(ev)
+        self._launch(xs, slot, m, out_score, out_valid, kw)
+
+    def _launch(self, xs, slot, m: int, out_score, out_valid, kw) -> None:
+        """The plan (or its graph) over the ``m`` device rows ``xs`` on the compute stream; then ring
+        slot ``slot`` (if any) is marked busy until that work is done."""
+        p = self.pipe
         g = self._graphs
         if g is not None and g.applies(m, kw):
             g.launch(xs, out_score, out_valid, stream=p.comp, **kw)
@@ -391,6 +449,9 @@ class StreamingScorer:
             return PredictionBatch.empty(0)
         if batch.n_features != self.F:
             raise ValueError(f"batch has {batch.n_features} features, model expects {self.F}")
+        if isinstance(batch, SparseRecordBatch) and self.F <= CSR_MAX_WIDTH:
+            # CSR over PCIe, expanded on the device; never touches batch.X (the host densification)
+            return self._submit(batch, self._stage_csr(batch, replace_nan), self._enqueue_csr, keep_device)
         X = batch.X
         if replace_nan is not None:  # sparse-absent entries only (host side: rare path)
             Xn = np.array(batch.numpy(), dtype=np.float32, copy=True)
@@ -412,6 +473,15 @@ class StreamingScorer:
                 X.record_stream(self.comp)
             elif not X.is_pinned() or X.dtype != torch.float32 or not X.is_contiguous():
                 X = _pin(X)
+        return self._submit(batch, X, self._enqueue, keep_device)
+
+    def _submit(self, batch: RecordBatch, X, enqueue, keep_device: bool) -> PredictionBatch:
+        """Output buffers, the ``micro_batch`` slices of the staged source ``X`` through
+        ``enqueue`` (:meth:`_enqueue` for a matrix, :meth:`_enqueue_csr` for a CSR source) and the
+        future over them."""
+        import torch
+
+        n = len(batch)
         self._throttle()
         score_h = torch.empty(n, dtype=torch.float32, pin_memory=True)
         valid_h = torch.empty(n, dtype=torch.uint8, pin_memory=True)
@@ -430,9 +500,9 @@ class StreamingScorer:
                 e = min(n, s + self.B)
                 if hs is not None:
                     kw = dict(score2=dev_out[0][s:e], valid2=dev_out[1][s:e]) if dev_out is not None else {}
-                    self._enqueue(X, s, e, hs + 4 * s, hv + s, kw)
+                    enqueue(X, s, e, hs + 4 * s, hv + s, kw)
                 else:
-                    self._enqueue(X, s, e, dev_out[0][s:e], dev_out[1][s:e], {})
+                    enqueue(X, s, e, dev_out[0][s:e], dev_out[1][s:e], {})
             done = torch.cuda.Event()
             if hs is None:
                 ev = torch.cuda.Event()
@@ -452,6 +522,72 @@ class StreamingScorer:
         METRICS.inc("scoring.batches_device")
         return PredictionBatch(n, score_h, valid_h, done, owner=(X, dev_out), on_done=_observe_latency,
                                device_out=dev_out, row_ok=batch.size_ok())
+
+    # ------------------------------------------------------------------ sparse (CSR) batches
+    def _stage_csr(self, batch: "SparseRecordBatch", replace_nan: Optional[float]) -> "_CsrSource":
+        """The pinned source of a sparse batch: its own arrays when they are pinned, else one
+        pinned copy of each (as dense input is staged), plus the per-slice ``indptr`` rebased to 0
+        in one pinned int32 array (slice ``j`` at ``j * (B + 1)``)."""
+        import torch
+
+        n, B, nnz = len(batch), self.B, batch.nnz
+        if nnz > len(batch.indices) or nnz > len(batch.values):
+            raise ValueError(f"sparse batch announces {nnz} entries, its arrays hold fewer")
+        with prange("score.stage"):
+            pinned = batch._pinned
+            if pinned is not None:
+                indices_t, values_t = pinned[1], pinned[2]
+            else:
+                indices_t = _pin_as(batch.indices[:nnz], torch.int32)
+                values_t = _pin_as(batch.values[:nnz], torch.float32)
+            n_slices = -(-n // B)
+            rebased = torch.empty(n + n_slices, dtype=torch.int32, pin_memory=True)
+            rb, ip = rebased.numpy(), batch.indptr
+            for j in range(n_slices):
+                s, e = j * B, min(n, (j + 1) * B)
+                np.subtract(ip[s:e + 1], ip[s], out=rb[s + j:e + j + 1], casting="unsafe")
+        fill = float("nan") if replace_nan is None else float(replace_nan)
+        METRICS.inc("scoring.rows_sparse_device", n)
+        METRICS.inc("scoring.h2d_bytes_sparse", 4 * (n + n_slices) + 8 * nnz)
+        # `batch` rides along: the arrays its pinned tensors view stay alive until the work is done
+        return _CsrSource(batch, ip, rebased, indices_t, values_t, fill)
+
+    def _enqueue_csr(self, src: "_CsrSource", s: int, e: int, out_score, out_valid, kw) -> None:
+        """H2D the CSR slice of rows ``[s, e)`` into the staging of the next ring slot, expand it
+        into the slot's dense rows on the compute stream, then launch the plan as :meth:`_enqueue`
+        does. The slot's events cover the staging: the next H2D into it waits for the expand
+        kernel and the plan that read it."""
+        from ..ops.sparse import csr_expand
+
+        p = self.pipe
+        m = e - s
+        k0, k1 = int(src.indptr[s]), int(src.indptr[e])
+        nnz = k1 - k0
+        if nnz < 0 or k0 < 0 or k1 > src.indices.numel():
+            raise ValueError(f"sparse batch: indptr[{s}:{e + 1}] = [{k0}, {k1}] is no range of its entries")
+        slot, xs = self._slot(m)
+        ip_d, idx_d, val_d = p.ensure_csr(slot, m, nnz)
+        j = s // self.B
+        h2ds = p.active_h2d()
+        if len(h2ds) > 1 and nnz * 8 < SPLIT_COPY_MIN_BYTES:
+            h2ds = h2ds[:1]
+        # one copy engine takes indptr + indices, a second (large slices only) the values
+        copies = [(ip_d.data_ptr(), src.rebased.data_ptr() + 4 * (s + j), 4 * (m + 1), 0),
+                  (idx_d.data_ptr(), src.indices.data_ptr() + 4 * k0, 4 * nnz, 0),
+                  (val_d.data_ptr(), src.values.data_ptr() + 4 * k0, 4 * nnz, len(h2ds) - 1)]
+        for i, st in enumerate(h2ds):
+            if p.used[slot]:
+                st.wait_event(p.ev_comp[slot])  # expand + plan finished reading this slot's staging
+            for dst, host, nbytes, lane in copies:
+                if lane == i and nbytes:
+                    rc = self._lib.pmml_memcpy_async(dst, host, nbytes, 1, st.cuda_stream)
+                    if rc != 0:
+                        raise RuntimeError(f"hipMemcpyAsync H2D failed ({rc})")
+            p.ev_h2d[slot][i].record(st)
+        for ev in p.ev_h2d[slot][: len(h2ds)]:
+            p.comp.wait_event(ev)
+        csr_expand(ip_d, idx_d, val_d, xs, nnz, src.fill, stream=p.comp)
+        self._launch(xs, slot, m, out_score, out_valid, kw)
 
     def score_row(self, x: np.ndarray) -> Tuple[float, bool]:
         """One record (``[F]`` values, NaN = missing) through the plan, synchronously: the

@@ -393,6 +393,35 @@ class DevicePlan:
         self.launch(Xt, score, valid, stream=stream)
         return score, valid.bool()
 
+    def score_csr(self, batch, replace_nan: Optional[float] = None, stream=None):
+        """:meth:`score` of a :class:`~flink_jpmml_amd.api.batch.SparseRecordBatch` without
+        densifying it on the host: its three CSR arrays go to the device, ``pmml_csr_expand``
+        rebuilds the ``[rows, n_features]`` matrix there (absent entries take ``replace_nan``, else
+        NaN; a stored NaN stays NaN), then :meth:`launch`. A batch wider than the kernel handles
+        takes the dense fallback."""
+        import torch
+
+        from ..ops.sparse import MAX_WIDTH, csr_expand
+
+        n = len(batch)
+        if batch.n_features != self.n_features:
+            raise ValueError(f"expected [rows, {self.n_features}] input, got {(n, batch.n_features)}")
+        if self.n_features > MAX_WIDTH:
+            return self.score(batch.X, replace_nan, stream=stream, absent=batch.absent)
+        nnz = batch.nnz
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            indptr = torch.from_numpy(np.ascontiguousarray(batch.indptr, dtype=np.int32)).to(self.device)
+            indices = torch.from_numpy(batch.indices[:nnz]).to(self.device)
+            values = torch.from_numpy(batch.values[:nnz]).to(self.device)
+            Xt = torch.empty((n, self.n_features), dtype=torch.float32, device=self.device)
+            score, valid = self.alloc_outputs(n)
+            if n:
+                fill = float("nan") if replace_nan is None else float(replace_nan)
+                csr_expand(indptr, indices, values, Xt, nnz, fill, stream=st)
+                self.launch(Xt, score, valid, stream=st)
+            return score, valid.bool()
+
 
 def _epilogue(mode: int, C: int = 1, a: float = 1.0, b: float = 0.0, thr: float = 0.5, table=None,
               write_probs: bool = False, link: int = 0, tgt: Optional[dict] = None):

@@ -147,6 +147,12 @@ class _RecordRows:
         self.pb, self.rows = pb, rows
 
 
+def _has_batches(values: List[Any]) -> bool:
+    """A chunk holds RecordBatch elements (any subclass, e.g. SparseRecordBatch): one pass over
+    the chunk's distinct types, not an ``isinstance`` per record."""
+    return any(issubclass(t, RecordBatch) for t in set(map(type, values)))
+
+
 def _futures_of(res: Any) -> List[PredictionBatch]:
     if type(res) is _RecordRows:
         return [res.pb]
@@ -512,7 +518,7 @@ class EvaluationFunction(FlatMapFunction, _ScoringMixin):
 
     def flat_map_many(self, values: List[Any], out: Collector) -> None:
         """Chunked delivery of per-record events (same results as element-wise)."""
-        if any(type(v) is RecordBatch for v in values):
+        if _has_batches(values):
             for v in values:
                 self.flat_map(v, out)
             return
@@ -710,7 +716,7 @@ class EvaluationCoFunction(CoProcessFunction, CheckpointedFunction, _ScoringMixi
     def process_elements1(self, events: List[Any], ctx, out: Collector) -> None:
         """Chunked delivery of per-record events (same results as element-wise)."""
         b = self._batcher
-        if any(type(e) is RecordBatch for e in events) or (b is not None and b.mode != "deferred"):
+        if _has_batches(events) or (b is not None and b.mode != "deferred"):
             for e in events:
                 self.process_element1(e, ctx, out)
             return
@@ -928,7 +934,7 @@ class QuickEvaluationFunction(FlatMapFunction, _ScoringMixin):
 
     def flat_map_many(self, values: List[Any], out: Collector) -> None:
         """Chunked delivery: per-record vectors are appended in bulk and flushed per full batch."""
-        has_rb = RecordBatch in set(map(type, values))
+        has_rb = _has_batches(values)
         if not self.config.batch_size or has_rb:
             if not self.config.batch_size and not has_rb:
                 model = self.inner.evaluator

@@ -606,8 +606,8 @@ class Executor:
             self.processed[id(n)] = sub[-1][0] + 1
             vals = [v for _, v in sub]
             self.elements_in += len(vals)
-            self.records_in += len(vals) if RecordBatch not in set(map(type, vals)) else \
-                sum(len(v) if type(v) is RecordBatch else 1 for v in vals)
+            self.records_in += len(vals) if not any(issubclass(t, RecordBatch) for t in set(map(type, vals))) else \
+                sum(len(v) if isinstance(v, RecordBatch) else 1 for v in vals)
             st.out.collect_many(vals)
             i = j
 
