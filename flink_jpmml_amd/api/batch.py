@@ -473,6 +473,128 @@ class SparseRecordBatch(RecordBatch):
         return f"SparseRecordBatch(rows={len(self)}, features={self.width}, nnz={self.nnz}{mid})"
 
 
+class _OutputCodec:
+    """What ``FieldSchema.decode`` needs for a set of output fields, detached from the document
+    (travels with a pickled :class:`BatchOutputs`)."""
+
+    def __init__(self, types: dict, values: dict):
+        self.types, self.values = types, values
+
+    def is_string(self, name: str) -> bool:
+        return self.types.get(name) == "string"
+
+    def decode(self, name: str, v: float) -> Any:
+        from ..pmml.fields import FieldSchema  # the one decode rule, over this object's types / values
+
+        return FieldSchema.decode(self, name, v)
+
+
+class BatchOutputs:
+    """The PMML ``<Output>`` fields (and top-k classes) of a scored batch, as columns.
+
+    ``matrix`` is ``[rows, len(names)]`` in document order: an fp32 torch tensor on the device that
+    scored it, float64 numpy on the host. Every value is a number: string-typed fields hold their
+    ``schema.lookup`` encoding (:meth:`decode` gives the Python values). ``top_index`` (int, −1 where
+    there is none) and ``top_probability`` are ``[rows, k]``; ``categories`` names the classes the
+    indices refer to."""
+
+    __slots__ = ("names", "matrix", "categories", "top_index", "top_probability", "_schema")
+
+    def __init__(self, names: Sequence[str], matrix: Any, schema: Any = None, categories: Optional[Sequence[str]] = None,
+                 top_index: Any = None, top_probability: Any = None):
+        self.names = list(names)
+        self.matrix = matrix
+        self.categories = list(categories) if categories is not None else None
+        self.top_index = top_index
+        self.top_probability = top_probability
+        self._schema = schema
+
+    @staticmethod
+    def from_wide(names: Sequence[str], wide: Any, k: int, schema: Any = None,
+                  categories: Optional[Sequence[str]] = None) -> "BatchOutputs":
+        """From ``[rows, len(names) + 2k]``: the fields, then the top-k class indices (NaN where
+        none), then their probabilities — the layout an ``OutputPlan`` writes."""
+        m = len(names)
+        ti = tp = None
+        if k:
+            raw = wide[:, m: m + k]
+            if hasattr(raw, "detach"):
+                import torch
+
+                ti = torch.where(torch.isnan(raw), torch.full_like(raw, -1.0), raw).long()
+            else:
+                ti = np.where(np.isnan(raw), -1, raw).astype(np.int64)
+            tp = wide[:, m + k: m + 2 * k]
+        return BatchOutputs(names, wide[:, :m], schema, categories, ti, tp)
+
+    def __len__(self) -> int:
+        return int(self.matrix.shape[0])
+
+    def __contains__(self, name: str) -> bool:
+        return name in self.names
+
+    def __getitem__(self, name: str):
+        return self.matrix[:, self.names.index(name)]
+
+    def numpy(self) -> "BatchOutputs":
+        """This object with host numpy arrays (waits for the device if need be)."""
+        def host(a):
+            return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+        return BatchOutputs(self.names, host(self.matrix), self._schema, self.categories,
+                            None if self.top_index is None else host(self.top_index),
+                            None if self.top_probability is None else host(self.top_probability))
+
+    def decode(self, name: str) -> List[Any]:
+        """Column ``name`` as Python values (``schema.decode``): strings for categorical fields,
+        ``None`` where the value is NaN."""
+        col = self[name]
+        if hasattr(col, "detach"):
+            col = col.detach().cpu().numpy()
+        col = np.asarray(col, dtype=np.float64)
+        if self._schema is None:
+            return [None if np.isnan(v) else float(v) for v in col]
+        return [None if np.isnan(v) else self._schema.decode(name, float(v)) for v in col]
+
+    def _wide_host(self) -> tuple:
+        h = self.numpy()
+        return (np.asarray(h.matrix), h.top_index, h.top_probability)
+
+    def masked(self, ok: np.ndarray) -> "BatchOutputs":
+        """Rows where ``ok`` is False hold NaN (−1 in ``top_index``); host arrays."""
+        m, ti, tp = self._wide_host()
+        ok = np.asarray(ok, dtype=bool)
+        m = np.where(ok[:, None], m, np.nan).astype(m.dtype, copy=False)
+        if ti is not None:
+            ti = np.where(ok[:, None], ti, -1)
+            tp = np.where(ok[:, None], tp, np.nan).astype(tp.dtype, copy=False)
+        return BatchOutputs(self.names, m, self._schema, self.categories, ti, tp)
+
+    @staticmethod
+    def concat(parts: Sequence["BatchOutputs"]) -> "BatchOutputs":
+        first = parts[0]
+        k = first.top_index is not None
+        for p in parts[1:]:
+            if p.names != first.names or p.categories != first.categories or (p.top_index is not None) != k \
+                    or (k and p.top_index.shape[1] != first.top_index.shape[1]):
+                raise ValueError("BatchOutputs.concat: the parts differ in fields, classes or top_k")
+        hosts = [p._wide_host() for p in parts]
+        return BatchOutputs(first.names, np.concatenate([h[0] for h in hosts]), first._schema, first.categories,
+                            np.concatenate([h[1] for h in hosts]) if k else None,
+                            np.concatenate([h[2] for h in hosts]) if k else None)
+
+    def __reduce__(self):  # pickles as host arrays + the fields' types and vocabularies (decode)
+        m, ti, tp = self._wide_host()
+        s = self._schema
+        if s is not None and not isinstance(s, _OutputCodec):
+            s = _OutputCodec({n: s.types.get(n) for n in self.names},
+                             {n: list(s.values.get(n, [])) for n in self.names if s.is_string(n)})
+        return (BatchOutputs, (self.names, np.array(m), s, self.categories, ti, tp))
+
+    def __repr__(self) -> str:
+        return f"BatchOutputs(rows={len(self)}, names={self.names})"
+
+
 class PredictionBatch:
     """Scores of one RecordBatch, possibly still being computed on the GPU.
 
@@ -485,11 +607,14 @@ class PredictionBatch:
     ``row_ok`` marks rows that passed the per-record size validation (others are EmptyScore)."""
 
     __slots__ = ("_n", "_scores", "_valid", "_done", "_owner", "_on_done", "_row_ok", "device_out", "submitted",
-                 "completed", "__weakref__")
+                 "completed", "_outputs", "__weakref__")
 
     def __init__(self, n: int, scores: Any = None, valid: Any = None, done: Any = None, owner: Any = None,
-                 on_done: Any = None, device_out: Any = None, row_ok: Optional[np.ndarray] = None):
+                 on_done: Any = None, device_out: Any = None, row_ok: Optional[np.ndarray] = None,
+                 outputs: Any = None):
         self._n = int(n)
+        # a BatchOutputs, or a callable building one from buffers that are complete once `done` is
+        self._outputs = outputs
         self._scores = scores
         self._valid = valid
         self._done = done
@@ -522,6 +647,13 @@ class PredictionBatch:
             v = v & ok
             s = np.where(ok, s, np.float32(np.nan)).astype(s.dtype, copy=False)
         self._scores, self._valid = s, v
+        o = self._outputs
+        if o is not None:
+            if callable(o):
+                o = o()
+            if ok is not None and not ok.all():
+                o = o.masked(ok)
+            self._outputs = o
         self.completed = time.perf_counter()
 
     def wait(self) -> "PredictionBatch":
@@ -549,6 +681,11 @@ class PredictionBatch:
     @property
     def valid(self) -> np.ndarray:
         return self.wait()._valid
+
+    @property
+    def outputs(self) -> Optional[BatchOutputs]:
+        """The batch's ``<Output>`` fields (``predict_records(..., outputs=True)``), else None."""
+        return self.wait()._outputs
 
     def values(self, default: float = float("nan")) -> np.ndarray:
         """Vectorised ``prediction.value.getOrElse(default)`` (float64)."""
@@ -610,14 +747,16 @@ class PredictionBatch:
         return f"PredictionBatch(rows={self._n}, {state})"
 
     def __reduce__(self):  # pickles as its (completed) arrays: checkpoint / all_gather_object safe
+        if self.outputs is not None:
+            return (PredictionBatch.from_arrays, (np.array(self.scores), np.array(self.valid), self.outputs))
         return (PredictionBatch.from_arrays, (np.array(self.scores), np.array(self.valid)))
 
     # ------------------------------------------------------------------ construction helpers
     @staticmethod
-    def from_arrays(scores: Any, valid: Any) -> "PredictionBatch":
+    def from_arrays(scores: Any, valid: Any, outputs: Optional[BatchOutputs] = None) -> "PredictionBatch":
         s = np.asarray(scores, dtype=np.float32)
         v = np.asarray(valid, dtype=bool)
-        return PredictionBatch(len(s), s, v)
+        return PredictionBatch(len(s), s, v, outputs=outputs)
 
     @staticmethod
     def empty(n: int) -> "PredictionBatch":
@@ -627,14 +766,18 @@ class PredictionBatch:
     def concat(parts: Sequence["PredictionBatch"]) -> "PredictionBatch":
         if not parts:
             return PredictionBatch.empty(0)
+        outs = [p.outputs for p in parts]
         return PredictionBatch.from_arrays(np.concatenate([p.scores for p in parts]),
-                                           np.concatenate([p.valid for p in parts]))
+                                           np.concatenate([p.valid for p in parts]),
+                                           BatchOutputs.concat(outs) if all(o is not None for o in outs) else None)
 
     def masked(self, ok: Optional[np.ndarray]) -> "PredictionBatch":
         """This batch with rows where ``ok`` is False forced to EmptyScore (validation failures)."""
         if ok is None or ok.all():
             return self
-        return PredictionBatch.from_arrays(np.where(ok, self.scores, np.nan), self.valid & ok)
+        outs = self.outputs
+        return PredictionBatch.from_arrays(np.where(ok, self.scores, np.nan), self.valid & ok,
+                                           None if outs is None else outs.masked(ok))
 
 
 def as_record_batch(x: Any, width: Optional[int] = None) -> Optional[RecordBatch]:
@@ -648,4 +791,4 @@ def as_record_batch(x: Any, width: Optional[int] = None) -> Optional[RecordBatch
     return None
 
 
-__all__ = ["PredictionBatch", "RecordBatch", "SparseRecordBatch", "as_record_batch", "as_vector"]
+__all__ = ["BatchOutputs", "PredictionBatch", "RecordBatch", "SparseRecordBatch", "as_record_batch", "as_vector"]

@@ -274,7 +274,9 @@ class PmmlModel(Pipeline):
 
     def predict_with_outputs(self, input_vector: Any, replace_nan: Optional[float] = None) -> Prediction:
         """Like :meth:`predict` but also returns the PMML ``<Output>`` fields in
-        ``Prediction.outputs`` (the reference extracts and drops them)."""
+        ``Prediction.outputs`` (the reference extracts and drops them). One record at a time on
+        the host; :meth:`predict_batch_outputs` and ``predict_records(batch, outputs=True)`` are
+        the batch forms (columns, on the GPU for a bound model)."""
         try:
             validated = self.validate_input(input_vector)
             prepared = self.prepare_input(validated, replace_nan)
@@ -297,10 +299,12 @@ class PmmlModel(Pipeline):
 
     # ------------------------------------------------------------------ batch API
     def predict_records(self, batch: RecordBatch, replace_nan: Optional[float] = None,
-                        keep_device: bool = False) -> PredictionBatch:
+                        keep_device: bool = False, outputs: bool = False, top_k: int = 0) -> PredictionBatch:
         """Columnar ``predict``: validation (row width), preparation, evaluation and extraction for
         a whole batch on the bound scorer. Never raises for bad records: rows the per-record path
-        would score as ``EmptyScore`` are invalid in the result."""
+        would score as ``EmptyScore`` are invalid in the result. ``outputs=True`` also computes the
+        model's ``<Output>`` fields (and the ``top_k`` most probable classes) into
+        ``PredictionBatch.outputs`` (a :class:`~flink_jpmml_amd.api.batch.BatchOutputs`)."""
         n = len(batch)
         if self.is_empty:  # EmptyEvaluatorException for every record -> EmptyScore
             return PredictionBatch.empty(n)
@@ -309,7 +313,28 @@ class PmmlModel(Pipeline):
             logger.warning("Error while validate input: batch width %d is not conform to model size %d",
                            batch.n_features, width)
             return PredictionBatch.empty(n)
+        if outputs:
+            return self.scorer.submit_batch(batch, replace_nan, keep_device=keep_device, outputs=True, top_k=top_k)
         return self.scorer.submit_batch(batch, replace_nan, keep_device=keep_device)
+
+    def predict_batch_outputs(self, X: Any, replace_nan: Optional[float] = None, device: Any = None,
+                              top_k: int = 0, **opts):
+        """:meth:`predict_batch` plus the model's ``<Output>`` fields: ``(scores, valid,
+        BatchOutputs)`` for a ``[rows, active_fields]`` matrix. ``device=None`` runs the float64
+        host oracle (numpy results), else the HIP output plan on that device (torch tensors).
+        ``top_k`` adds the ``k`` most probable classes per row (``BatchOutputs.top_index`` /
+        ``top_probability``; ties go to the lower class, NaN probabilities are never selected)."""
+        from .batch import BatchOutputs
+
+        compiled = self.evaluator.model
+        if device is None:
+            from ..runtime.outputs import host_batch_outputs
+
+            return host_batch_outputs(compiled, np.asarray(X.detach().cpu().numpy() if hasattr(X, "detach") else X),
+                                      replace_nan, None, top_k)
+        plan = compiled.output_plan(device, top_k=top_k, **opts)
+        s, v, wide = plan.score_outputs(X, replace_nan=replace_nan)
+        return s, v, BatchOutputs.from_wide(plan.names, wide, plan.top_k, compiled.schema, plan.categories)
 
     def predict_batch(self, X: Any, replace_nan: Optional[float] = None, device: Any = None, **opts):
         """Score a ``[rows, active_fields]`` matrix (numpy or torch; NaN = missing) or a sequence

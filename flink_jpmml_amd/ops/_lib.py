@@ -265,7 +265,16 @@ class CsrExpandArgs(ctypes.Structure):
                 ("m", c_int), ("F", c_int), ("nnz", c_int), ("fill", c_float)]
 
 
+class OutputArgs(ctypes.Structure):
+    """outputs.hip OutputArgs: raw index-mode results of ``m`` rows -> their ``n_col`` output columns."""
+    _fields_ = [("score", c_void_p), ("valid", c_void_p), ("probs", c_void_p), ("affinity", c_void_p),
+                ("prog", c_void_p), ("tables", c_void_p), ("label_table", c_void_p), ("out", c_void_p),
+                ("score_out", c_void_p), ("valid_out", c_void_p), ("m", c_int), ("C", c_int), ("ldp", c_int),
+                ("n_col", c_int), ("ldo", c_int), ("k", c_int), ("n_tables", c_int), ("n_labels", c_int)]
+
+
 _ABI = {
+    "pmml_outputs_args_size": OutputArgs,
     "pmml_csr_expand_args_size": CsrExpandArgs,
     "pmml_segment_args_size": SegArgs,
     "pmml_textparse_args_size": TextParseArgs,
@@ -403,6 +412,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_csr_expand.restype = c_int
         lib.pmml_csr_expand_rows.argtypes = [c_int]
         lib.pmml_csr_expand_rows.restype = c_int
+        lib.pmml_outputs_launch.argtypes = [c_void_p, ctypes.POINTER(OutputArgs)]
+        lib.pmml_outputs_launch.restype = c_int
+        lib.pmml_outputs_rows.argtypes = [c_int, c_int]
+        lib.pmml_outputs_rows.restype = c_int
         _lib = lib
         return lib
 

@@ -108,7 +108,30 @@ class CompiledPmml:
         v = v & ok
         return np.where(v, s, np.nan), v
 
+    def outputs_matrix_oracle(self, X: np.ndarray, replace_nan: Optional[float] = None,
+                              absent: Optional[np.ndarray] = None) -> tuple:
+        """``(scores, valid, {output field: float64 column})`` from one vectorised oracle pass:
+        :meth:`score_matrix_oracle`'s score / valid pair plus the encoded ``<Output>`` columns
+        (NaN in every column of a row that fails preparation)."""
+        from .outputs import oracle_outputs
+
+        s, v, cols, _, _ = oracle_outputs(self, X, replace_nan, absent)
+        return s, v, cols
+
     # ------------------------------------------------------------------ device
+    def output_plan(self, device: Any = "cuda", top_k: int = 0, **opts):
+        """The :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan` of this model, lowered once per
+        (device, top_k, options) and cached like :meth:`plan`."""
+        from .outputs import OutputPlan
+
+        key = f"outputs|{device}|{int(top_k)}|{sorted(opts.items())}"
+        with self._lock:
+            p = self._plans.get(key)
+            if p is None:
+                p = OutputPlan(self, device, top_k=top_k, **opts)
+                self._plans[key] = p
+            return p
+
     def plan(self, device: Any = "cuda", **opts):
         """Lower to device tensors once per (device, options) and cache the plan."""
         from .plans import compile_plan

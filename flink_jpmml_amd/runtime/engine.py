@@ -252,6 +252,11 @@ class StreamingScorer:
         self.max_inflight = int(max_inflight)
         self._inflight: "collections.deque" = collections.deque()
         self.rows_submitted = 0
+        # Output-field plans by top_k, lowered on first use under the config's policy (make_scorer)
+        self._out_plans: dict = {}
+        self._out_lock = threading.Lock()
+        self.fallback = "warn"
+        self.lowering_opts: dict = {}
         self._row_state = None  # score_row's persistent buffers
         self._row_lock = threading.Lock()  # ...shared by every caller of score_row
         from ..ops import _lib
@@ -342,7 +347,10 @@ class StreamingScorer:
         slot ``slot`` (if any) is marked busy until that work is done."""
         p = self.pipe
         g = self._graphs
-        if g is not None and g.applies(m, kw):
+        if kw.get("outputs") is not None:  # the Output fields route: the output plan, never a graph
+            kw = dict(kw)
+            kw.pop("plan").launch(xs, out_score, out_valid, stream=p.comp, **kw)
+        elif g is not None and g.applies(m, kw):
             g.launch(xs, out_score, out_valid, stream=p.comp, **kw)
         else:
             self.plan.launch(xs, out_score, out_valid, stream=p.comp, **kw)
@@ -434,14 +442,51 @@ class StreamingScorer:
         while self._inflight and self._inflight[0][0].query():
             self._inflight.popleft()
 
+    def _output_plan(self, top_k: int):
+        """The model's :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan`, lowered on first use;
+        a :class:`HostScorer` instead when it does not lower and the fallback policy allows."""
+        op = self._out_plans.get(top_k)
+        if op is not None:
+            return op
+        with self._out_lock:  # one lowering, one warning and one fallback count per top_k
+            op = self._out_plans.get(top_k)
+            if op is None:
+                op = self._out_plans[top_k] = self._lower_outputs(top_k)
+        return op
+
+    def _lower_outputs(self, top_k: int):
+        """:meth:`_output_plan`'s first use (under its lock): lower, or fall back as the policy says."""
+        from .plans import NotLowerable
+
+        compiled = getattr(self.plan, "compiled", None)
+        if compiled is None or not hasattr(compiled, "output_plan"):
+            from ..api.exceptions import UnsupportedFeatureException
+
+            raise UnsupportedFeatureException(
+                "Output fields need the PMML document: this scorer's plan arrived by replication "
+                "without it (bind the model from its document on this rank)")
+        try:
+            return compiled.output_plan(self.device, top_k=top_k, **self.lowering_opts)
+        except NotLowerable as e:
+            if self.fallback == "error":
+                raise
+            METRICS.inc("scoring.host_fallback_outputs")
+            if self.fallback == "warn":
+                logger.warning("Output fields of model %r cannot run on %s (%s): computing them on the "
+                               "host oracle (set fallback='error' to refuse)", compiled.model_name, self.device, e)
+            return HostScorer(compiled, reason=str(e))
+
     def submit_batch(self, batch: RecordBatch, replace_nan: Optional[float] = None,
-                     keep_device: bool = False) -> PredictionBatch:
+                     keep_device: bool = False, outputs: bool = False, top_k: int = 0) -> PredictionBatch:
         """Enqueue a whole RecordBatch; returns its :class:`PredictionBatch` future immediately.
 
         ``X`` may be pinned host memory (copied in ``micro_batch`` slices on the H2D stream),
         pageable host memory (staged through one pinned copy) or device memory (scored in place).
         ``keep_device`` additionally keeps ``[n]`` device mirrors of the outputs
-        (``PredictionBatch.device_out``, for an all-gather sink)."""
+        (``PredictionBatch.device_out``, for an all-gather sink). ``outputs`` also computes the
+        model's ``<Output>`` fields and the ``top_k`` classes (``PredictionBatch.outputs``): the
+        output plan writes device buffers, one D2H copy brings scores, validity and the output
+        matrix back (the zero-copy host sink is not used on this route)."""
         import torch
 
         n = len(batch)
@@ -449,9 +494,14 @@ class StreamingScorer:
             return PredictionBatch.empty(0)
         if batch.n_features != self.F:
             raise ValueError(f"batch has {batch.n_features} features, model expects {self.F}")
+        op = None
+        if outputs:
+            op = self._output_plan(int(top_k))
+            if isinstance(op, HostScorer):
+                return op.submit_batch(batch, replace_nan, outputs=True, top_k=top_k)
         if isinstance(batch, SparseRecordBatch) and self.F <= CSR_MAX_WIDTH:
             # CSR over PCIe, expanded on the device; never touches batch.X (the host densification)
-            return self._submit(batch, self._stage_csr(batch, replace_nan), self._enqueue_csr, keep_device)
+            return self._submit(batch, self._stage_csr(batch, replace_nan), self._enqueue_csr, keep_device, op)
         X = batch.X
         if replace_nan is not None:  # sparse-absent entries only (host side: rare path)
             Xn = np.array(batch.numpy(), dtype=np.float32, copy=True)
@@ -473,12 +523,13 @@ class StreamingScorer:
                 X.record_stream(self.comp)
             elif not X.is_pinned() or X.dtype != torch.float32 or not X.is_contiguous():
                 X = _pin(X)
-        return self._submit(batch, X, self._enqueue, keep_device)
+        return self._submit(batch, X, self._enqueue, keep_device, op)
 
-    def _submit(self, batch: RecordBatch, X, enqueue, keep_device: bool) -> PredictionBatch:
+    def _submit(self, batch: RecordBatch, X, enqueue, keep_device: bool, out_plan=None) -> PredictionBatch:
         """Output buffers, the ``micro_batch`` slices of the staged source ``X`` through
         ``enqueue`` (:meth:`_enqueue` for a matrix, :meth:`_enqueue_csr` for a CSR source) and the
-        future over them."""
+        future over them. With ``out_plan`` every slice runs the output plan into device buffers
+        and the ``[n, width]`` output matrix comes back with the scores."""
         import torch
 
         n = len(batch)
@@ -487,7 +538,8 @@ class StreamingScorer:
         valid_h = torch.empty(n, dtype=torch.uint8, pin_memory=True)
         dev_out = None
         hs = hv = None
-        if self.direct:
+        out_h = out_d = None
+        if self.direct and out_plan is None:
             hs, hv = self.pipe.host_dev_ptr(score_h), self.pipe.host_dev_ptr(valid_h)
             if hs is None or hv is None:
                 hs = hv = None
@@ -495,12 +547,18 @@ class StreamingScorer:
             with torch.cuda.stream(self.comp):
                 dev_out = (torch.empty(n, dtype=torch.float32, device=self.device),
                            torch.empty(n, dtype=torch.uint8, device=self.device))
+        if out_plan is not None:
+            out_h = torch.empty((n, out_plan.width), dtype=torch.float32, pin_memory=True)
+            with torch.cuda.stream(self.comp):
+                out_d = torch.empty((n, out_plan.width), dtype=torch.float32, device=self.device)
         with prange("score.enqueue"):
             for s in range(0, n, self.B):
                 e = min(n, s + self.B)
                 if hs is not None:
                     kw = dict(score2=dev_out[0][s:e], valid2=dev_out[1][s:e]) if dev_out is not None else {}
                     enqueue(X, s, e, hs + 4 * s, hv + s, kw)
+                elif out_plan is not None:
+                    enqueue(X, s, e, dev_out[0][s:e], dev_out[1][s:e], dict(outputs=out_d[s:e], plan=out_plan))
                 else:
                     enqueue(X, s, e, dev_out[0][s:e], dev_out[1][s:e], {})
             done = torch.cuda.Event()
@@ -511,6 +569,9 @@ class StreamingScorer:
                     self.d2h.wait_event(ev)
                     score_h.copy_(dev_out[0], non_blocking=True)
                     valid_h.copy_(dev_out[1], non_blocking=True)
+                    if out_d is not None:
+                        out_h.copy_(out_d, non_blocking=True)
+                        out_d.record_stream(self.d2h)
                     for t in dev_out:
                         t.record_stream(self.d2h)
                 done.record(self.d2h)
@@ -520,8 +581,14 @@ class StreamingScorer:
         self.rows_submitted += n
         METRICS.inc("scoring.rows_device", n)
         METRICS.inc("scoring.batches_device")
-        return PredictionBatch(n, score_h, valid_h, done, owner=(X, dev_out), on_done=_observe_latency,
-                               device_out=dev_out, row_ok=batch.size_ok())
+        outputs = None
+        if out_plan is not None:
+            from ..api.batch import BatchOutputs
+
+            names, k, schema, cats = out_plan.names, out_plan.top_k, out_plan.compiled.schema, out_plan.categories
+            outputs = lambda: BatchOutputs.from_wide(names, out_h.numpy(), k, schema, cats)  # noqa: E731
+        return PredictionBatch(n, score_h, valid_h, done, owner=(X, dev_out, out_d), on_done=_observe_latency,
+                               device_out=dev_out, row_ok=batch.size_ok(), outputs=outputs)
 
     # ------------------------------------------------------------------ sparse (CSR) batches
     def _stage_csr(self, batch: "SparseRecordBatch", replace_nan: Optional[float]) -> "_CsrSource":
@@ -674,20 +741,26 @@ class HostScorer:
         self.F = compiled.n_features
 
     def submit_batch(self, batch: RecordBatch, replace_nan: Optional[float] = None,
-                     keep_device: bool = False) -> PredictionBatch:
+                     keep_device: bool = False, outputs: bool = False, top_k: int = 0) -> PredictionBatch:
         n = len(batch)
         if n == 0:
             return PredictionBatch.empty(0)
         if batch.n_features != self.F:
             raise ValueError(f"batch has {batch.n_features} features, model expects {self.F}")
         t0 = time.perf_counter()
+        outs = None
         with prange("score.host"):
-            s, v = self.compiled.score_matrix_oracle(batch.numpy(), replace_nan, batch.absent)
+            if outputs:
+                from .outputs import host_batch_outputs
+
+                s, v, outs = host_batch_outputs(self.compiled, batch.numpy(), replace_nan, batch.absent, top_k)
+            else:
+                s, v = self.compiled.score_matrix_oracle(batch.numpy(), replace_nan, batch.absent)
         METRICS.inc("scoring.rows_host", n)
         if self.reason is not None:
             METRICS.inc("scoring.host_fallback_rows", n)
         METRICS.observe("scoring.batch_latency_ms", (time.perf_counter() - t0) * 1e3)
-        return PredictionBatch(n, s.astype(np.float32), v, row_ok=batch.size_ok())
+        return PredictionBatch(n, s.astype(np.float32), v, row_ok=batch.size_ok(), outputs=outs)
 
     def drain(self) -> None:
         pass
@@ -700,12 +773,18 @@ class NullScorer:
     kind = "null"
     direct = False
 
-    def __init__(self, n_features: int):
+    def __init__(self, n_features: int, compiled=None):
         self.F = n_features
+        self.compiled = compiled
 
     def submit_batch(self, batch: RecordBatch, replace_nan: Optional[float] = None,
-                     keep_device: bool = False) -> PredictionBatch:
+                     keep_device: bool = False, outputs: bool = False, top_k: int = 0) -> PredictionBatch:
         METRICS.inc("scoring.empty_score.no_target", len(batch))
+        if outputs and self.compiled is not None and len(batch) and batch.n_features == self.F:
+            from .outputs import host_batch_outputs  # every score is empty, the Output fields are not
+
+            s, v, outs = host_batch_outputs(self.compiled, batch.numpy(), replace_nan, batch.absent, top_k)
+            return PredictionBatch(len(batch), s.astype(np.float32), v, row_ok=batch.size_ok(), outputs=outs)
         return PredictionBatch.empty(len(batch))
 
     def drain(self) -> None:
@@ -735,7 +814,7 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
 
     cfg = config or ScoringConfig()
     if not compiled.target_fields:
-        return NullScorer(compiled.n_features)
+        return NullScorer(compiled.n_features, compiled)
     if cfg.host_threads:
         _set_host_threads(cfg.host_threads)
     if device is None:
@@ -759,7 +838,9 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
             return HostScorer(compiled, reason=str(e))
     if pipeline is None:
         pipeline = DevicePipeline(plan.device, cfg.micro_batch, cfg.pipeline_depth, cfg.h2d_streams)
-    return StreamingScorer(plan, pipeline=pipeline, max_inflight=cfg.max_inflight, graph_max_rows=cfg.graph_max_rows)
+    scorer = StreamingScorer(plan, pipeline=pipeline, max_inflight=cfg.max_inflight, graph_max_rows=cfg.graph_max_rows)
+    scorer.fallback, scorer.lowering_opts = cfg.fallback, dict(cfg.lowering_opts())
+    return scorer
 
 
 __all__ = ["DevicePipeline", "HostScorer", "NullScorer", "StepHandle", "StreamingScorer", "make_scorer"]

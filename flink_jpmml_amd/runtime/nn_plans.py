@@ -224,6 +224,7 @@ class MlpPlan(DevicePlan):
                     raise NotLowerable("classification outputs must be NormDiscrete on output neurons")
                 labels[out_neurons.index(o.neuron)] = ex.value
             self.table = self._t(_label_table([x if x is not None else "nan" for x in labels]))
+            self.labels = list(labels)  # class of each output unit (runtime/outputs.py)
             self.out_a, self.out_b = 1.0, 0.0
             self.target_stage = None
         else:

@@ -374,6 +374,13 @@ class DevicePlan:
     def score(self, X: Any, replace_nan: Optional[float] = None, stream=None, absent: Any = None):
         """Score a host (numpy) or device (torch) matrix; returns device tensors ``(score, valid)``.
         ``replace_nan`` fills the ``absent`` entries (every NaN when no mask is given)."""
+        Xt = self._device_matrix(X, replace_nan, absent)
+        score, valid = self.alloc_outputs(Xt.shape[0])
+        self.launch(Xt, score, valid, stream=stream)
+        return score, valid.bool()
+
+    def _device_matrix(self, X: Any, replace_nan: Optional[float] = None, absent: Any = None):
+        """The contiguous fp32 device matrix :meth:`score` launches on."""
         import torch
 
         if isinstance(X, np.ndarray):
@@ -389,9 +396,7 @@ class DevicePlan:
             else:
                 mask = torch.as_tensor(np.asarray(absent, dtype=bool)).to(self.device)
                 Xt = torch.where(mask, torch.full_like(Xt, float(replace_nan)), Xt)
-        score, valid = self.alloc_outputs(Xt.shape[0])
-        self.launch(Xt, score, valid, stream=stream)
-        return score, valid.bool()
+        return Xt
 
     def score_csr(self, batch, replace_nan: Optional[float] = None, stream=None):
         """:meth:`score` of a :class:`~flink_jpmml_amd.api.batch.SparseRecordBatch` without
@@ -401,26 +406,37 @@ class DevicePlan:
         takes the dense fallback."""
         import torch
 
-        from ..ops.sparse import MAX_WIDTH, csr_expand
+        from ..ops.sparse import MAX_WIDTH
 
         n = len(batch)
         if batch.n_features != self.n_features:
             raise ValueError(f"expected [rows, {self.n_features}] input, got {(n, batch.n_features)}")
         if self.n_features > MAX_WIDTH:
             return self.score(batch.X, replace_nan, stream=stream, absent=batch.absent)
-        nnz = batch.nnz
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(st):
-            indptr = torch.from_numpy(np.ascontiguousarray(batch.indptr, dtype=np.int32)).to(self.device)
-            indices = torch.from_numpy(batch.indices[:nnz]).to(self.device)
-            values = torch.from_numpy(batch.values[:nnz]).to(self.device)
-            Xt = torch.empty((n, self.n_features), dtype=torch.float32, device=self.device)
+            Xt = self._csr_device_matrix(batch, replace_nan, st)
             score, valid = self.alloc_outputs(n)
             if n:
-                fill = float("nan") if replace_nan is None else float(replace_nan)
-                csr_expand(indptr, indices, values, Xt, nnz, fill, stream=st)
                 self.launch(Xt, score, valid, stream=st)
             return score, valid.bool()
+
+    def _csr_device_matrix(self, batch, replace_nan: Optional[float], st):
+        """The sparse batch's arrays on the device, expanded into its dense fp32 matrix on ``st``
+        (the current stream)."""
+        import torch
+
+        from ..ops.sparse import csr_expand
+
+        n, nnz = len(batch), batch.nnz
+        indptr = torch.from_numpy(np.ascontiguousarray(batch.indptr, dtype=np.int32)).to(self.device)
+        indices = torch.from_numpy(batch.indices[:nnz]).to(self.device)
+        values = torch.from_numpy(batch.values[:nnz]).to(self.device)
+        Xt = torch.empty((n, self.n_features), dtype=torch.float32, device=self.device)
+        if n:
+            fill = float("nan") if replace_nan is None else float(replace_nan)
+            csr_expand(indptr, indices, values, Xt, nnz, fill, stream=st)
+        return Xt
 
 
 def _epilogue(mode: int, C: int = 1, a: float = 1.0, b: float = 0.0, thr: float = 0.5, table=None,

@@ -762,54 +762,17 @@ class ChainPlan(DevicePlan):
     def _expr_program(self, compiled, col: dict, seg: int):
         """``(DerivedProgram, insns, pool, out_cols, [augmented column of each output])`` computing
         segment ``seg``'s expression outputs in document order, or None."""
-        from .derive import INSN_DTYPE, OP_STORE, STACK_DEPTH, DerivedProgram, _Emitter
-
         exprs = [(c, ex) for s_, c, _, _, _, ex in self.outs if s_ == seg and ex is not None]
         if not exprs:
             return None
-        n_in = len(self.columns)
-        if n_in + len(exprs) > 256:
-            raise NotLowerable("chain expression outputs: more than 256 augmented columns")
-        col_of = dict(col)
-        em = _Emitter(compiled.schema, col_of)
-        derived = []
-        for j, (c, ex) in enumerate(exprs):
-            name = self.columns[c]
-            em.expr(ex, name)
-            dt = compiled.schema.types.get(name)
-            em.emit(OP_STORE, a=n_in + j, c=2 if dt == "integer" else 0, pops=1)
-            col_of[name] = n_in + j  # later expressions read the fresh value
-            derived.append(name)
-        if em.max_sp > STACK_DEPTH:
-            raise NotLowerable(f"chain expression output needs a stack of {em.max_sp} > {STACK_DEPTH}")
-        insns = np.array(em.insns, dtype=INSN_DTYPE)
-        prog = DerivedProgram(list(self.columns), derived, derived, insns, np.array(em.pool or [0.0]), em.max_sp)
-        return (prog, self._t(insns.view(np.int32).reshape(-1)), self._t(prog.pool), self._t(prog.out_cols),
+        prog = expression_program(compiled.schema, self.columns, col, [(self.columns[c], ex, None) for c, ex in exprs],
+                                  "chain expression output")
+        return (prog, self._t(prog.insns.view(np.int32).reshape(-1)), self._t(prog.pool), self._t(prog.out_cols),
                 [c for c, _ in exprs])
 
     def _run_expr(self, ep, Xa, st):
         """The derive program over the augmented matrix -> ``[n, outputs]`` fp32."""
-        import ctypes
-
-        import torch
-
-        from ..ops._lib import DeriveArgs, check, ptr, stream_handle
-        from .derive import emulate
-
-        prog, insns, pool, out_cols, _ = ep
-        n = Xa.shape[0]
-        if self.device.type != "cuda":  # lowering dry run (CPU tests): the kernel's numpy twin
-            return torch.from_numpy(emulate(prog, Xa.double().numpy()))
-        out = torch.empty((n, len(prog.selected)), dtype=torch.float32, device=self.device)
-        ok = torch.empty(n, dtype=torch.uint8, device=self.device)
-        a = DeriveArgs()
-        a.X = Xa.data_ptr()
-        a.n_rows, a.n_in, a.ldx, a.n_tile = n, Xa.shape[1], Xa.stride(0), prog.n_tile
-        a.prep, a.prog, a.pool, a.out_cols = None, ptr(insns), ptr(pool), ptr(out_cols)
-        a.n_insn, a.n_sel = len(prog.insns), len(prog.selected)
-        a.out, a.row_ok = ptr(out), ptr(ok)
-        check(self.lib.pmml_derive_launch(stream_handle(st), ctypes.byref(a)), "chain output derive kernel")
-        return out
+        return run_expression_program(self.device, self.lib, ep, Xa, st, "chain output derive kernel")
 
     def launch(self, X, score, valid, stream=None, probs=None, score2=None, valid2=None, **kw) -> None:
         import torch
@@ -881,6 +844,61 @@ class ChainPlan(DevicePlan):
                     vo.copy_(best_v.to(torch.uint8))
 
 
+def expression_program(schema, columns: List[str], col_of: dict, exprs, what: str):
+    """Output expressions as one derive program (``ops/csrc/derive.hip``) over the ``columns`` of an
+    augmented matrix. ``exprs``: ``(output name, expression, newly visible {name: column} or None)``
+    in document order; each result is stored in a fresh tile column past ``columns`` and later
+    expressions read it under its name. Returns the :class:`DerivedProgram` whose selected columns
+    are the expression outputs, in order."""
+    from .derive import INSN_DTYPE, OP_STORE, STACK_DEPTH, DerivedProgram, _Emitter
+
+    n_in = len(columns)
+    if n_in + len(exprs) > 256:
+        raise NotLowerable(f"{what}s: more than 256 augmented columns")
+    col_of = dict(col_of)
+    em = _Emitter(schema, col_of)
+    derived = []
+    for j, (name, ex, reveal) in enumerate(exprs):
+        if reveal:
+            col_of.update(reveal)
+        em.expr(ex, name)
+        dt = schema.types.get(name)
+        em.emit(OP_STORE, a=n_in + j, c=2 if dt == "integer" else 0, pops=1)
+        col_of[name] = n_in + j  # later expressions read the fresh value
+        derived.append(name)
+    if em.max_sp > STACK_DEPTH:
+        raise NotLowerable(f"{what} needs a stack of {em.max_sp} > {STACK_DEPTH}")
+    insns = np.array(em.insns, dtype=INSN_DTYPE)
+    return DerivedProgram(list(columns), derived, derived, insns, np.array(em.pool or [0.0]), em.max_sp)
+
+
+def run_expression_program(device, lib, ep, Xa, st, what: str = "output derive kernel"):
+    """An :func:`expression_program` (``ep``: the program and its device ``insns`` / ``pool`` /
+    ``out_cols``) over the augmented matrix ``Xa`` on stream ``st`` -> ``[n, outputs]`` fp32. On a
+    dry-run device (``cpu``) the kernel's numpy twin runs instead."""
+    import ctypes
+
+    import torch
+
+    from ..ops._lib import DeriveArgs, check, ptr, stream_handle
+    from .derive import emulate
+
+    prog, insns, pool, out_cols = ep[:4]
+    n = Xa.shape[0]
+    if device.type != "cuda":  # lowering dry run (CPU tests): the kernel's numpy twin
+        return torch.from_numpy(emulate(prog, Xa.double().numpy()))
+    out = torch.empty((n, len(prog.selected)), dtype=torch.float32, device=device)
+    ok = torch.empty(n, dtype=torch.uint8, device=device)
+    a = DeriveArgs()
+    a.X = Xa.data_ptr()
+    a.n_rows, a.n_in, a.ldx, a.n_tile = n, Xa.shape[1], Xa.stride(0), prog.n_tile
+    a.prep, a.prog, a.pool, a.out_cols = None, ptr(insns), ptr(pool), ptr(out_cols)
+    a.n_insn, a.n_sel = len(prog.insns), len(prog.selected)
+    a.out, a.row_ok = ptr(out), ptr(ok)
+    check(lib.pmml_derive_launch(stream_handle(st), ctypes.byref(a)), what)
+    return out
+
+
 class _Cols:
     """compile_predicate's view of the chain's augmented columns."""
 
@@ -902,4 +920,4 @@ def _median0(A):
     return torch.where(cnt > 0, (lo + hi) / 2, torch.full_like(lo, float("nan")))
 
 
-__all__ = ["ChainPlan", "ChainView", "SegmentedPlan", "SubView", "probs_width", "segmentable"]
+__all__ = ["ChainPlan", "ChainView", "SegmentedPlan", "SubView", "expression_program", "probs_width", "segmentable"]
