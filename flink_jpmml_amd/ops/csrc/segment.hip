@@ -200,8 +200,7 @@ __global__ __launch_bounds__(SEG_TB) void segment_reduce_kernel(SegArgs a) {
         out = lab >= 0 ? (double)a.table[lab] : __builtin_nan("");
         ok = ok && out == out;
       } else {
-        out = (double)s;
-        ok = ok && isfinite(out);
+        out = (double)s;  // an infinite chosen value stays a prediction (_select tests isnan only; okmask did)
         if (a.tgt) out = seg_target(a, out);
       }
     } else if (!a.classification && a.tgt) {

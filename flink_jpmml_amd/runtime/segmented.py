@@ -550,7 +550,8 @@ class SegmentedPlan(DevicePlan):
             v = v & ~torch.isnan(s)
             return s, v
         s = s.double()
-        s, v = apply_target_torch(s, v & torch.isfinite(s), self.tgt)
+        # the oracle's _select keeps an infinite chosen value (it tests isnan only, as ``ok`` did)
+        s, v = apply_target_torch(s, v, self.tgt)
         return s, v
 
     def _regress(self, S, ok, T):
