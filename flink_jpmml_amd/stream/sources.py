@@ -160,7 +160,8 @@ class TextBatchSource(SourceFunction):
     ``parse="device"`` (or ``"auto"`` on a GPU box, when every used field is numeric) moves the raw
     bytes to the GPU and parses them there (:mod:`~flink_jpmml_amd.stream.device_text`): batches
     are then device-resident, ``device_chunk_bytes`` of text each, bit-identical to the host
-    parser."""
+    parser. ``delimiter`` must not be a byte that can occur inside a number (``.``, ``e``, ``E``,
+    ``+``, ``-``, a digit): host and device would split such lines differently."""
 
     chunkable = False  # each batch is a large parse: hand it downstream as soon as it exists
 
