@@ -225,7 +225,8 @@ class NnPrepArgs(ctypes.Structure):
 class LinearArgs(ctypes.Structure):
     _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("K", c_int),
                 ("prep", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("simplemax", c_int), ("pad", c_int),
-                ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p), ("probs", c_void_p)]
+                ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p), ("probs", c_void_p),
+                ("listed", c_void_p)]
 
 
 class MlpArgs(ctypes.Structure):

@@ -3,7 +3,9 @@
 //
 // One lane per row; W and b are read with wave-uniform addresses (scalar loads, broadcast), the
 // row tile comes from the shared LDS staging helper. A missing numeric predictor makes the row's
-// prediction missing (PMML RegressionModel rule).
+// prediction missing (PMML RegressionModel rule). A predictor that table k does not list is not
+// multiplied into y_k (listed[f] bit k; the dense W holds 0 there, and 0 * inf would be NaN where
+// the oracle never forms the product); an explicit coefficient of 0 is listed and multiplied.
 #include "epilogue.h"
 
 namespace {
@@ -22,6 +24,7 @@ struct LinearArgs {
   float* score;
   uint8_t* valid;
   float* probs;
+  const uint32_t* listed;  // [F] bit k: table k lists predictor f; NULL: every table lists every predictor
 };
 
 __global__ __launch_bounds__(TB) void linear_kernel(LinearArgs a) {
@@ -41,9 +44,10 @@ __global__ __launch_bounds__(TB) void linear_kernel(LinearArgs a) {
     const float x = feat[f * TB + tid];
     miss = miss || (x != x);
     const float* w = a.W + (size_t)f * a.K;
+    const uint32_t m = a.listed ? a.listed[f] : 0xFFFFu;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
-      if (k < a.K) acc[k] = fmaf(w[k], x, acc[k]);
+      if (k < a.K && ((m >> k) & 1u)) acc[k] = fmaf(w[k], x, acc[k]);
   }
   if (a.simplemax) {
     float s = 0.f;
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(TB) void linear_kernel(LinearArgs a) {
     for (int k = 0; k < KMAX; ++k)
       if (k < a.K) acc[k] /= s;
   }
-  apply_epilogue(a.epi, [&](int c) {
+  apply_epilogue<true>(a.epi, [&](int c) {
     float v = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) v = (k == c) ? acc[k] : v;
@@ -72,6 +76,10 @@ PMML_API int pmml_linear_launch(hipStream_t stream, const LinearArgs* args) {
   if (a.K > KMAX || a.n_feat > 128) return -4;
   const size_t lds = (size_t)a.n_feat * TB * 4 + TB * 4;
   dim3 grid((a.n_rows + TB - 1) / TB);
+  // 64 fields and more stage past 64 KiB of LDS
+  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(linear_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -5;
   hipLaunchKernelGGL(linear_kernel, grid, dim3(TB), lds, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }

@@ -368,7 +368,10 @@ __global__ __launch_bounds__(TB, 2) void tree_compact_kernel(TreeArgs a) {
       const uint32_t lv = nodes[pos[i]].x;
       if (GENERAL) {
         const int slot = a.tree_slot[t0 + i];
-        for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)lv * a.P + p];
+        // P == 1 (class slots of a K-class chain): the leaf slot holds the value, not a leaf-table row
+        if (a.P == 1) accl[slot * TB + tid] += __uint_as_float(lv);
+        else
+          for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)lv * a.P + p];
       } else {
         acc += __uint_as_float(lv);
       }
@@ -470,7 +473,10 @@ __global__ __launch_bounds__(TB, 2) void tree_super_kernel(TreeArgs a) {
       }
       if (GENERAL) {
         const int slot = a.tree_slot[t0 + i];
-        for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)leafv[i] * a.P + p];
+        // P == 1 (class slots of a K-class chain): the leaf slot holds the value, not a leaf-table row
+        if (a.P == 1) accl[slot * TB + tid] += __uint_as_float(leafv[i]);
+        else
+          for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)leafv[i] * a.P + p];
       } else {
         acc += __uint_as_float(leafv[i]);
       }
@@ -625,7 +631,10 @@ __global__ __launch_bounds__(TB, 2) void tree_rank3_kernel(TreeArgs a) {
       if (i >= nt) break;
       if (GENERAL) {
         const int slot = a.tree_slot[t0 + i];
-        for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)leafv[i] * a.P + p];
+        // P == 1 (class slots of a K-class chain): the leaf slot holds the value, not a leaf-table row
+        if (a.P == 1) accl[slot * TB + tid] += __uint_as_float(leafv[i]);
+        else
+          for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)leafv[i] * a.P + p];
       } else {
         acc += __uint_as_float(leafv[i]);
       }

@@ -176,7 +176,11 @@ __global__ __launch_bounds__(TB, 2) void tree_hybrid_kernel(HybridArgs ha) {
         }
         if (GENERAL) {
           const int slot = a.tree_slot[c0 + k + i];
-          for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)val[i] * a.P + p];
+          // class slots with one value per leaf (K-class chains): the leaf slot holds the value
+          // itself (pack_hybrid_compact, P == 1), not a row of the leaf table
+          if (a.P == 1) accl[slot * TB + tid] += __uint_as_float(val[i]);
+          else
+            for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)val[i] * a.P + p];
         } else if (a.P > 1) {
           acc += a.leaves[(size_t)val[i] * a.P];
         } else {

@@ -188,11 +188,13 @@ __global__ __launch_bounds__(LT, 1) void tree_lds_kernel(LdsTreeArgs la) {
             const uint32_t lv = nodes[pos].x;
             if (GENERAL) {
               const int slot = a.tree_slot[t];
-              const float* lp = a.leaves + (size_t)lv * a.P;
+              // P == 1 (class slots of a K-class chain): the leaf slot holds the value itself, not
+              // a row of the leaf table
+              const float* lp = a.leaves + (a.P == 1 ? (size_t)0 : (size_t)lv * a.P);
 #pragma unroll
               for (int k = 0; k < LCMAX; ++k) {
                 const int p = k - slot;
-                if (p >= 0 && p < a.P) accv[k] += lp[p];
+                if (p >= 0 && p < a.P) accv[k] += a.P == 1 ? __uint_as_float(lv) : lp[p];
               }
             } else {
               acc += __uint_as_float(lv);

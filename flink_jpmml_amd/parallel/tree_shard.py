@@ -64,7 +64,7 @@ def finish_epilogue(raw: torch.Tensor, valid: torch.Tensor, epi: dict, labels=No
         s, ok = apply_target_torch(s, ok, epi.get("tgt"))
     elif epi["mode"] == EPI_LOGISTIC2:
         label = (y < epi.get("thr", 0.5)).long()  # p0 >= thr -> class 0
-        ok = ok & ~torch.isnan(y)
+        ok = ok & torch.isfinite(y)  # the oracle: p0 and 1 - p0 finite
         if labels is not None:
             # the kernel's table: non-numeric labels are NaN -> the row is invalid (EmptyScore)
             tab = torch.as_tensor(_label_table(list(labels)), dtype=raw.dtype, device=raw.device)

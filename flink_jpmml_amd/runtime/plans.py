@@ -700,7 +700,8 @@ class KnnPlan(DevicePlan):
 
 class LinearPlan(DevicePlan):
     kind = "linear"
-    _STATE = DevicePlan._STATE + ("W", "b", "K", "simplemax", "table", "epi_args")
+    _STATE = DevicePlan._STATE + ("W", "b", "K", "simplemax", "table", "epi_args", "listed")
+    MAX_TABLES, MAX_FIELDS = 16, 128  # csrc/linear.hip: KMAX accumulators per lane, LDS planes per field
 
     def __init__(self, compiled, device):
         super().__init__(compiled, device)
@@ -712,6 +713,9 @@ class LinearPlan(DevicePlan):
             # reorder W rows to the active-field order
             pass
         W, b = ev.dense_weights()
+        if W.shape[1] > self.MAX_TABLES or compiled.n_features > self.MAX_FIELDS:
+            raise NotLowerable(f"linear kernel holds {self.MAX_TABLES} tables x {self.MAX_FIELDS} fields, got "
+                               f"{W.shape[1]} x {compiled.n_features}")
         Wf = np.zeros((compiled.n_features, W.shape[1]))
         for i, name in enumerate(ev.numeric_fields):
             if name not in compiled.active_fields:
@@ -725,6 +729,14 @@ class LinearPlan(DevicePlan):
         self.W = self._t(Wf.astype(np.float32))
         self.b = self._t(b.astype(np.float32))
         self.K = W.shape[1]
+        # bit k of listed[f]: table k lists predictor f. The oracle never multiplies a predictor a
+        # table does not list, so the dense 0 there must not meet an infinite input (0 * inf = NaN);
+        # None when every table lists every predictor
+        listed = np.zeros(compiled.n_features, dtype=np.int64)
+        for k, t in enumerate(ev.rm.tables):
+            for p in t.numeric:
+                listed[compiled.active_fields.index(p.name)] |= 1 << k
+        self.listed = None if (listed == (1 << self.K) - 1).all() else self._t(listed.astype(np.int32))
         norm = ev.rm.normalization_method
         self.simplemax = 0
         if ev.kind == "classification":
@@ -774,6 +786,7 @@ class LinearPlan(DevicePlan):
         a.epi = _epilogue(table=self.table, write_probs=probs is not None, **self.epi_args)
         a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
         a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
+        a.listed = ptr(getattr(self, "listed", None))
         check(self.lib.pmml_linear_launch(stream_handle(stream), ctypes.byref(a)), "linear kernel")
 
 
