@@ -34,6 +34,12 @@ class KernelLibraryError(RuntimeError):
     pass
 
 
+# Per-source flags, after the common ones. derive.hip is the fp64 interpreter of derived fields: no
+# fused multiply-add, neither in its own arithmetic (the float64 oracle has none) nor inside the
+# inlined fp64 library functions (fused, sin / cos / tan lose their argument reduction above 2^30).
+SOURCE_FLAGS = {"derive.hip": ["-ffp-contract=off"]}
+
+
 def sources() -> List[str]:
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
@@ -91,7 +97,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, incremental
         dep_t = max(os.path.getmtime(d) for d in _deps(src))
         if incremental and os.path.exists(obj) and os.path.getmtime(obj) > dep_t:
             continue
-        cmd = [cc, *flags, "-c", src, "-o", obj]
+        cmd = [cc, *flags, *SOURCE_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
         if verbose:
             logger.info("%s", " ".join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

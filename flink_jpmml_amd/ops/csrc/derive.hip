@@ -14,6 +14,10 @@
 //    coalesced): the augmented, already-prepared input matrix of the model kernel that runs next.
 // Program arithmetic is fp64 like the host oracle (pmml/fields.py::eval_expression); stored
 // columns are rounded to fp32 (every model kernel consumes fp32 features).
+// This file is compiled with -ffp-contract=off (ops/_lib.py::SOURCE_FLAGS). Under -ffp-contract=fast
+// the backend also fuses multiply-adds inside the inlined fp64 library functions, which breaks the
+// error-free steps of the large-argument reduction of sin / cos / tan: from |x| = 2^30 on they
+// returned the sine of another angle (tests/test_gpu_derive.py, the rounded family).
 #include "common.h"
 
 namespace {
@@ -77,13 +81,13 @@ __device__ __forceinline__ double unary(int fn, double v) {
     case F_SINH: return sinh(v);
     case F_COSH: return cosh(v);
     case F_TANH: return tanh(v);
-    case F_EXPM1: return expm1(v);
-    case F_LN1P: return log1p(v);
+    case F_EXPM1: return v == 0.0 ? v : expm1(v);   // C99: expm1(-0.0) and log1p(-0.0) are -0.0; the
+    case F_LN1P: return v == 0.0 ? v : log1p(v);    // device functions were measured to give +0.0
     case F_NOT: return v == 0.0 ? 1.0 : 0.0;
     case F_ERF: return erf(v);
     case F_SNCDF: return normcdf(v);
     case F_SNPDF: return exp(-0.5 * v * v) * 0.3989422804014327;  // 1 / sqrt(2 pi)
-    case F_SNIDF: return normcdfinv(v);
+    case F_SNIDF: return normcdfinv(v) + 0.0;       // normcdfinv(0.5) is -0.0 here, the oracle's ndtri +0.0
     default: return __builtin_nan("");
   }
 }

@@ -579,6 +579,41 @@ def _ndtri(a):
     return ndtri(a)
 
 
+def _erfc(a):
+    from scipy.special import erfc
+
+    return erfc(a)
+
+
+def _ncdf(z):
+    """Standard normal CDF in the cancellation-free form (``0.5 * (1 + erf(z / sqrt 2))`` is 0 below
+    z = -8.3, where the value is 5e-17 and still an fp32 number down to z = -14)."""
+    return 0.5 * _erfc(-z / _SQRT2)
+
+
+def nan_min(stack: np.ndarray) -> np.ndarray:
+    """Column minimum of the present values; among zeros -0.0 orders below +0.0 (Java's
+    ``Math.min``; ``np.nanmin`` returns whichever zero comes first)."""
+    r = np.nanmin(stack, axis=0)
+    return np.where((r == 0) & ((stack == 0) & np.signbit(stack)).any(axis=0), -0.0, r)
+
+
+def nan_max(stack: np.ndarray) -> np.ndarray:
+    r = np.nanmax(stack, axis=0)
+    return np.where((r == 0) & ((stack == 0) & ~np.signbit(stack)).any(axis=0), 0.0, r)
+
+
+def nan_median(stack: np.ndarray) -> np.ndarray:
+    """Column median of the present values from a stable sort: zeros of either sign compare equal and
+    keep their argument order, as in the device's insertion sort (``np.nanmedian`` partitions, which
+    leaves the sign of a zero median to chance)."""
+    s = np.sort(stack, axis=0, kind="stable")  # NaN last
+    m = (~np.isnan(stack)).sum(axis=0)
+    cols = np.arange(stack.shape[1])
+    lo, hi = s[np.maximum(m - 1, 0) // 2, cols], s[np.minimum(m // 2, len(s) - 1), cols]
+    return np.where(m == 0, NAN, np.where(m & 1, hi, 0.5 * (lo + hi)))
+
+
 _SQRT2 = math.sqrt(2.0)
 _SQRT2PI = math.sqrt(2.0 * math.pi)
 
@@ -588,7 +623,7 @@ _BINARY_NUM: Dict[str, Callable] = {
 }
 # PMML 4.4 distribution functions: f(x, mean, stdev)
 _TERNARY_NUM: Dict[str, Callable] = {
-    "normalCDF": lambda x, m, s: 0.5 * (1.0 + _erf((x - m) / (s * _SQRT2))),
+    "normalCDF": lambda x, m, s: _ncdf((x - m) / s),
     "normalPDF": lambda x, m, s: np.exp(-0.5 * ((x - m) / s) ** 2) / (s * _SQRT2PI),
     "normalIDF": lambda p, m, s: m + s * _ndtri(p),
 }
@@ -597,7 +632,7 @@ _UNARY_NUM: Dict[str, Callable] = {
     "ceil": np.ceil, "round": lambda a: np.floor(a + 0.5), "rint": np.rint, "sin": np.sin, "cos": np.cos,
     "tan": np.tan, "asin": np.arcsin, "acos": np.arccos, "atan": np.arctan, "sinh": np.sinh, "cosh": np.cosh,
     "tanh": np.tanh, "expm1": np.expm1, "ln1p": np.log1p, "erf": _erf,
-    "stdNormalCDF": lambda a: 0.5 * (1.0 + _erf(a / _SQRT2)),
+    "stdNormalCDF": _ncdf,
     "stdNormalPDF": lambda a: np.exp(-0.5 * a * a) / _SQRT2PI,
     "stdNormalIDF": _ndtri,
 }
@@ -758,8 +793,10 @@ def _eval_apply(ex: ir.Apply, cols: Columns, out_field: Optional[str]) -> np.nda
             miss = cnt == 0
         elif fn in ("min", "max", "sum", "avg", "product", "median") and args:
             stack = np.vstack(args)
-            res = {"min": np.nanmin, "max": np.nanmax, "sum": np.nansum, "avg": np.nanmean, "product": np.nanprod,
-                   "median": np.nanmedian}[fn](stack, axis=0)
+            if fn in ("min", "max", "median"):
+                res = {"min": nan_min, "max": nan_max, "median": nan_median}[fn](stack)
+            else:
+                res = {"sum": np.nansum, "avg": np.nanmean, "product": np.nanprod}[fn](stack, axis=0)
             miss = np.all(np.isnan(stack), axis=0)
         elif fn in ("equal", "notEqual", "lessThan", "lessOrEqual", "greaterThan", "greaterOrEqual"):
             op = {"equal": np.equal, "notEqual": np.not_equal, "lessThan": np.less, "lessOrEqual": np.less_equal,

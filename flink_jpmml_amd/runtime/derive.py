@@ -26,7 +26,8 @@ The program mirrors :func:`flink_jpmml_amd.pmml.fields.eval_expression` (the flo
 instruction for instruction; :func:`emulate` is its numpy twin, used by the CPU tests to pin the
 lowering against the oracle without a GPU. Stored columns are fp32 (as every model kernel
 consumes); a ``double`` derived field that feeds *another* derived field is therefore rounded to
-fp32 in between (the oracle keeps fp64) — the only numeric difference, documented in the tests.
+fp32 in between (the oracle keeps fp64) — the only numeric difference, listed in docs/PARITY.md and
+pinned by tests/test_derive_cases.py::test_fp32_columns_between_chained_fields.
 """
 
 from __future__ import annotations
@@ -747,7 +748,19 @@ _NP_BINARY = {0: np.add, 1: np.subtract, 2: np.multiply, 3: np.divide, 4: np.pow
               7: np.arctan2,
               10: np.equal, 11: np.not_equal, 12: np.less, 13: np.less_equal, 14: np.greater,
               15: np.greater_equal, 16: np.greater}
-_NP_NARY = {50: np.nanmin, 51: np.nanmax, 52: np.nansum, 53: np.nanmean, 54: np.nanprod, 55: np.nanmedian}
+
+
+def _fields(name: str):
+    from ..pmml import fields
+
+    fn = getattr(fields, name)
+    return lambda st, axis=0: fn(st)
+
+
+# min / max: -0.0 orders below +0.0 (the hardware's fmin / fmax and Java's Math.min / Math.max); median:
+# a stable sort, as the kernel's insertion sort
+_NP_NARY = {50: _fields("nan_min"), 51: _fields("nan_max"), 52: np.nansum, 53: np.nanmean, 54: np.nanprod,
+            55: _fields("nan_median")}
 
 
 def _apply_np(fn: int, args: List[np.ndarray], x: float, y: float, n: int) -> np.ndarray:

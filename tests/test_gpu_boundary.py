@@ -356,9 +356,11 @@ def test_derive_program_twin_on_the_edges(dtype):
 def test_derive_kernel_on_the_edges(gpu, dtype):
     """``derive.hip``: ``Discretize`` with all four closures, inputs at the bin edges +-2 ulps
     (bit-exact: the score spells every field's bin), and ``NormContinuous`` at its knots. The
-    interpolation runs in fp32 on fp32-rounded knots: |error| <= a few ulps of the value times the
-    coefficient, 256 * 8 * 2**-24 < 2e-4, against jumps of 63 (or 63 * 256) when an input falls on
-    the wrong side of an outer knot — so 1e-3 separates the two."""
+    interpolation runs in float64 on float64 knots, as in the oracle; each column is then rounded to
+    fp32 once (tests/test_gpu_derive.py pins the columns bit for bit) and the regression behind it
+    sums in fp32: a score of up to 64 + 256 * 64 carries half an fp32 ulp, 2**13 * 2**-24 < 5e-4, plus
+    the two column roundings times their coefficients, against jumps of 63 (or 63 * 256) when an
+    input falls on the wrong side of an outer knot — so 1e-3 separates the two."""
     from flink_jpmml_amd.runtime.derive import DerivedPlan
 
     X = _derive_inputs()
