@@ -18,6 +18,7 @@ oracle is documented per test.
 
 from __future__ import annotations
 
+import collections
 import dataclasses
 import logging
 import math
@@ -1355,6 +1356,68 @@ def _pointer_pack(trees: List[BinaryTree], weights: List[float], P: int):
 # XCD-aware tree slicing of pointer / hybrid forests (csrc tree_block): one slice per XCD
 XCD_SLICES = 8
 
+# TreePlan's lowering options as its builders read them (see TreePlan.__init__ for what each does)
+_TreeOptions = collections.namedtuple("_TreeOptions", (
+    "lds_budget variant precision nan_mode max_chunk_trees head_depth pointer_schedule node_order node_format "
+    "pointer_ilp xcd_split pointer_load hybrid_tail pointer_leaf"))
+_OPTION_VALUES = (  # (option, what it may be, the refusal), in the order they are checked
+    ("nan_mode", ("auto", "off"), "nan_mode must be 'auto' or 'off'"),
+    ("pointer_ilp", (2, 4, 6, 8, 16), "pointer_ilp must be 2, 4, 6 (LTOP only), 8 or 16"),
+    ("pointer_schedule", ("refill", "lockstep"), "pointer_schedule must be 'refill' or 'lockstep'"),
+    ("pointer_load", ("auto", "clamped", "masked", "uskip", "peel", "ltop"),
+     "pointer_load must be 'auto', 'clamped', 'masked', 'uskip', 'peel' or 'ltop'"),
+    ("hybrid_tail", ("compact", "wide"), "hybrid_tail must be 'compact' or 'wide'"),
+    ("pointer_leaf", ("table", "inline"), "pointer_leaf must be 'table' or 'inline'"),
+    ("xcd_split", ("on", "off"), "xcd_split must be 'on' or 'off'"),
+    ("precision", ("fp32", "fp8"), "tree leaf precision must be fp32 or fp8"),
+)
+
+
+def _validated(o: _TreeOptions) -> _TreeOptions:
+    """The options, checked, with ``pointer_load="auto"`` resolved."""
+    for name, allowed, refusal in _OPTION_VALUES:
+        if getattr(o, name) not in allowed:
+            raise ValueError(refusal)
+    load = o.pointer_load
+    if load == "auto":
+        table8 = o.pointer_ilp == 8 and o.pointer_leaf == "table"  # the 8-walk lock-step kernel with table leaves
+        load = ("ltop" if o.node_order == "bfs" else "peel") if table8 else "clamped"
+    return o._replace(pointer_ilp=int(o.pointer_ilp), pointer_load=load)
+
+
+def _pointer_variant(layout: str, schedule: str, load: str, order: str, ilp: int, feat_lds: bool,
+                     node_format: Optional[str], inline: bool) -> int:
+    """Variant bits of a pointer / hybrid plan: the node format's kernel, else the refill
+    schedule, else (pointer layout, features in LDS) the lock-step walk's load scheme."""
+    formats = {"rank3": VAR_POINTER_RANK3, "super": VAR_POINTER_SUPER, "lds": VAR_POINTER_LDS,
+               "compact": VAR_POINTER_COMPACT}
+    if node_format in formats:
+        return formats[node_format]
+    if layout == "pointer" and schedule == "refill":
+        return VAR_POINTER_REFILL  # each PILP slot restarts on the next tree as soon as its walk ends
+    if layout == "pointer" and feat_lds:
+        if load == "masked":
+            return VAR_POINTER_MASKED  # finished walks skip their node load (exec mask)
+        if load == "peel":
+            return VAR_POINTER_PEEL  # top two levels from wave-uniform scalar loads
+        if load == "ltop" and order == "bfs" and ilp in (6, 8):
+            return VAR_POINTER_LTOP | (VAR_POINTER_INLINE if inline else 0)  # levels 0-4 from LDS
+        if load == "uskip":
+            return VAR_POINTER_USKIP  # slots finished in the whole wave issue no load
+    return VAR_POINTER_INLINE if inline else 0  # leaf payloads inline: no leaf gather
+
+
+def _onehot_leaf_pairs(leaves: np.ndarray) -> Optional[np.ndarray]:
+    """Vote leaves as ``{class, weight}`` pairs when every leaf row has at most one non-zero
+    payload (pointer_walk reads one 8-byte pair and updates one slot instead of P), else None."""
+    L = np.asarray(leaves, dtype=np.float32).reshape(len(leaves), -1)
+    nz = L != 0
+    if not (nz.sum(axis=1) <= 1).all():
+        return None
+    cls = np.where(nz.any(axis=1), nz.argmax(axis=1), 0).astype(np.int32)
+    w = L[np.arange(len(L)), cls].astype(np.float32)
+    return np.stack([cls, w.view(np.int32)], axis=1).view(np.float32)
+
 
 class TreePlan(DevicePlan):
     """GBDT / random forest / single tree / calibrated chain on the HIP traversal kernel."""
@@ -1369,11 +1432,24 @@ class TreePlan(DevicePlan):
                                   "lds_rows", "lds_chunk_u4", "lds_n_slices", "mix_mass", "mix_w", "mix_tab",
                                   "mix_remap", "vcol", "leaf_onehot")
 
-    # GENERAL-layout extras (sibling mixtures, per-record leaf columns); None on every other layout
-    mix_mass = mix_w = mix_tab = mix_remap = vcol = None
-    leaf_onehot = 0  # pointer walks of one-hot votes: leaves as {class, weight} pairs
-
     WIDE_G = 4  # tree groups of the wide kernel (mirrors csrc)
+    LDS_SLICES = 8  # XCD slices of the LDS-resident walk (one per XCD: tree_lds.hip)
+
+    # What a state attribute holds on a layout that does not use it: a builder assigns only what
+    # its layout uses, and a plan rebuilt by ``from_state`` has its state set over these. (The
+    # state attributes not named here are set for every layout.)
+    variant = mode = rec_words = chunk_trees = 0
+    rows_wide = TB
+    blob = leaves = roots = slots = table = None
+    blob_nan, chunk_trees_nan = None, 0  # wide PERFECT kernel: NaN -> +inf second feature plane
+    tree_w = acc_init = feat_map = None  # wide PERFECT kernel
+    children, preds, pool, trees_tab, max_steps = None, None, None, None, 0  # GENERAL layout (predicate VM)
+    mix_mass = mix_w = mix_tab = mix_remap = vcol = None  # ... sibling mixtures, per-record leaf columns
+    heads, head_depth, tail_format, xcd_split = None, 0, 0, 0  # hybrid layout (xcd_split: pointer too)
+    rank_thr, rank_cnt, rank_stride = None, None, 0  # rank3 node format
+    lds_chunks, lds_slices, lds_rows, lds_chunk_u4, lds_n_slices = None, None, 0, 0, 0  # lds node format
+    leaf_onehot = 0  # pointer walks of one-hot votes: leaves as {class, weight} pairs
+    prof = None  # kbench --tree-prof phase timers, set from outside (nullable)
 
     def __init__(self, compiled, device, layout: str = "auto", lds_budget: int = 80 * 1024, splits: int = 0,
                  variant: str = "auto", precision: str = "fp32", nan_mode: str = "auto", max_chunk_trees: int = 0,
@@ -1428,32 +1504,10 @@ class TreePlan(DevicePlan):
         emit the RAW weighted leaf sum (the full epilogue is kept in ``full_epi`` and applied after
         the cross-rank ``all_reduce``, :mod:`flink_jpmml_amd.parallel.tree_shard`)."""
         super().__init__(compiled, device)
-        if nan_mode not in ("auto", "off"):
-            raise ValueError("nan_mode must be 'auto' or 'off'")
-        if pointer_ilp not in (2, 4, 6, 8, 16):
-            raise ValueError("pointer_ilp must be 2, 4, 6 (LTOP only), 8 or 16")
-        self.pointer_ilp = int(pointer_ilp)
-        if pointer_schedule not in ("refill", "lockstep"):
-            raise ValueError("pointer_schedule must be 'refill' or 'lockstep'")
-        self.heads, self.head_depth = None, 0  # hybrid layout only
-        self.lds_chunks = self.lds_slices = None  # lds node format only
-        self.lds_rows = self.lds_chunk_u4 = self.lds_n_slices = 0
-        self.rank_thr, self.rank_cnt, self.rank_stride = None, None, 0  # rank3 node format only
-        if pointer_load not in ("auto", "clamped", "masked", "uskip", "peel", "ltop"):
-            raise ValueError("pointer_load must be 'auto', 'clamped', 'masked', 'uskip', 'peel' or 'ltop'")
-        if pointer_load == "auto":
-            pointer_load = (("ltop" if node_order == "bfs" else "peel") if (pointer_ilp == 8 and pointer_leaf == "table")
-                            else "clamped")
-        if hybrid_tail not in ("compact", "wide"):
-            raise ValueError("hybrid_tail must be 'compact' or 'wide'")
-        if pointer_leaf not in ("table", "inline"):
-            raise ValueError("pointer_leaf must be 'table' or 'inline'")
-        self.tail_format = 0
-        if xcd_split not in ("on", "off"):
-            raise ValueError("xcd_split must be 'on' or 'off'")
-        self.xcd_split = 0
-        if precision not in ("fp32", "fp8"):
-            raise ValueError("tree leaf precision must be fp32 or fp8")
+        opt = _validated(_TreeOptions(lds_budget, variant, precision, nan_mode, max_chunk_trees, head_depth,
+                                      pointer_schedule, node_order, node_format, pointer_ilp, xcd_split, pointer_load,
+                                      hybrid_tail, pointer_leaf))
+        self.pointer_ilp = opt.pointer_ilp
         if layout == "general":
             spec = self._general_spec(compiled)
         else:
@@ -1470,313 +1524,282 @@ class TreePlan(DevicePlan):
             if layout == "general":
                 raise NotLowerable("tree sharding needs the binary (perfect / pointer) layouts")
             spec = shard_spec(spec, *tree_shard)
-        self.spec = spec
         self.epi_args = dict(spec.epi)
-        F = compiled.n_features
-        depth = max(1, max(t.depth for t in spec.trees))
-        self.depth = depth
-        self.n_trees = len(spec.trees)
+        F = self.n_stage = compiled.n_features
+        depth = self.depth = max(1, max(t.depth for t in spec.trees))
         if layout == "general":
-            if precision == "fp8":
-                raise NotLowerable("fp8 leaves need the PERFECT layout")
-            from .general_tree import pack_general
-
-            if spec.mode == "slot" and any(b != 0.0 for b in (spec.acc_init or [])):
-                raise NotLowerable("K-class chains with intercepts over non-binary trees are host-only")
-            spec = to_general(spec)
-            self.spec = spec
-            self.n_trees = len(spec.trees)
-
-            g = pack_general(spec.trees, spec.weights, spec.P, compiled.schema)
-            self.mode, self.tree_w, self.acc_init, self.feat_map = 0, None, None, None
-            self.rows_wide, self.n_stage = TB, F
-            self.layout, self.variant, self.rec_words, self.chunk_trees = "general", 0, 0, 0
-            self.blob_nan, self.chunk_trees_nan = None, 0
-            self.P, self.C = spec.P, spec.C
-            self.general = 1 if spec.P > 1 else 0
-            self.blob = self._t(g["nodes"].reshape(-1))
-            self.children = self._t(g["children"])
-            self.preds = self._t(g["preds"].reshape(-1))
-            self.pool = self._t(g["pool"])
-            self.trees_tab = self._t(g["trees"].reshape(-1))
-            self.leaves = self._t(g["payload"].reshape(-1))
-            mix = g["mix_mass"] is not None
-            self.mix_mass = self._t(g["mix_mass"].reshape(-1)) if mix else None
-            self.mix_w = self._t(g["mix_w"]) if mix else None
-            self.mix_tab = self._t(g["mix_tab"].reshape(-1)) if mix else None
-            self.mix_remap = self._t(g["remap"]) if mix else None
-            self.vcol = self._t(g["vcol"]) if g["vcol"] is not None else None
-            self.roots = None
-            self.max_steps = g["max_steps"]
-            self.has_dr = False
-            self.table = self._t(_label_table(spec.labels)) if spec.labels is not None else None
-            self.slots = self._t(np.zeros(self.n_trees, dtype=np.int32)) if self.general else None
-            self.splits = 1
-            self._partial = None
-            return
-        self.children = self.preds = self.pool = self.trees_tab = None
-        self.max_steps = 0
-        self.heads, self.head_depth = None, 0
-        NI, NL = (1 << depth) - 1, 1 << depth
-        # wide kernel geometry: stage only the columns the trees read (+ columns whose preparation
-        # can reject a row); row tiles of 256 / 128 / 64 rows keep the feature planes <= 64 KiB
-        stage = self._stage_columns(compiled, spec.trees)
-        rows = next((r for r, lim in ((256, 64), (128, 128), (64, 256)) if len(stage) <= lim), None)
-        wide_ok = (spec.P == 1 and depth <= 10 and rows is not None and variant != "narrow"
-                   and (spec.mode == "sum" or spec.C <= 8))
-        if layout == "auto":
-            rec_bytes = 4 * (2 * NI + NL * spec.P + (NI + 31) // 32)
-            # deeper trees: the POINTER walk (profiles/r3q: 300 trees x depth 14, pointer 3.39 /
-            # 2.60 ms vs hybrid-head 4.55 / 3.11 ms for the forest / GBDT)
-            layout = "perfect" if depth <= 10 and (wide_ok or F <= 64) and rec_bytes <= 32 * 1024 else "pointer"
-        if spec.mode != "sum" and not (layout == "perfect" and wide_ok):
-            spec = to_general(spec)  # votes / class slots accumulate in LDS on the narrow kernels
-            self.n_trees = len(spec.trees)  # + constant stumps carrying the per-class intercepts
-        self.spec = spec
-        self.layout = layout
-        self.P, self.C = spec.P, spec.C
-        self.general = 1 if (spec.P > 1 or (spec.mode == "sum" and spec.slots is not None)) else 0
-        self.mode = {"sum": 0, "slot": 1, "class": 2}[spec.mode]
-        self.tree_w = self.acc_init = self.feat_map = None
-        self.rows_wide, self.n_stage = TB, F
-        if self.layout == "perfect":
-            if variant == "auto":
-                variant = "narrow" if self.general or not wide_ok else "wide"
-            self.variant = 1 if variant == "wide" else 0
-            if self.variant == 1:
-                if not wide_ok:
-                    raise NotLowerable("the wide tree kernel needs P = 1 and <= 256 staged columns")
-                self.rows_wide, self.n_stage = rows, len(stage)
-                stride = rows  # [F][rows] planes: traversal reads hit bank row mod 32 (csrc WideGeom)
-                fmap = {f: j for j, f in enumerate(stage)}
-                if stage != list(range(F)):
-                    self.feat_map = self._t(np.array(stage, dtype=np.int32))
-            else:
-                if F > 64:
-                    raise NotLowerable("the narrow perfect kernel stages at most 64 features")
-                stride, fmap = TB, None
-            leaf_bits = None
-            if spec.mode == "class":
-                self.mode = self._vote_mode(spec, rows)
-                if self.mode == 3:  # VOTE8: packed u8 counters, the leaf is the increment 1 << 8*class
-                    leaf_bits = "vote8"
-                elif spec.tree_w is not None and any(w != 1.0 for w in spec.tree_w):
-                    self.tree_w = self._t(np.asarray(spec.tree_w, np.float32))
-            if spec.mode == "slot":
-                if spec.acc_init is not None and any(b != 0.0 for b in spec.acc_init):
-                    self.acc_init = self._t(np.asarray(spec.acc_init, np.float32))
-            blob, rec, has_dr = _perfect_pack(spec.trees, spec.weights, spec.P, depth, stride=stride, fmap=fmap,
-                                              leaf_bits=leaf_bits)
-            nan_flags = 0
-            blob_nan = None
-            Fs = self.n_stage
-            if self.variant == 1 and nan_mode == "auto" and not any(t.null_missing for t in spec.trees):
-                if not has_dr:
-                    nan_flags = VAR_NAN_FAST
-                elif precision != "fp8" or (2 * Fs - 1) * stride * 4 < (1 << 16):  # fp8 metas: 16-bit offsets
-                    blob_nan = _nan_planes(blob, depth, Fs, stride)
-                    nan_flags = VAR_NAN_FAST | VAR_NAN_PLANES
-            if self.variant == 1 and self.mode == 3 and precision != "fp8" and depth >= 2 \
-                    and (Fs * 2 if blob_nan is not None else Fs) * stride * 4 <= (1 << 16):
-                # VOTE8 forest: class codes in the last-level metas (no leaf array, no leaf read)
-                blob, rec = _vote_codes_pack(blob, depth)
-                if blob_nan is not None:
-                    blob_nan, _ = _vote_codes_pack(blob_nan, depth)
-                self.variant = 2
-            if precision == "fp8":
-                # e4m3 leaves in the last-level metas, global scale folded into the epilogue
-                if self.general or self.variant != 1 or spec.mode != "sum":
-                    raise NotLowerable("fp8 leaves need the single-accumulator wide kernel (P = 1)")
-                if (Fs - 1) * stride * 4 >= (1 << 16):
-                    raise NotLowerable("fp8 leaf pairs need feature offsets below 64 KiB")
-                blob, rec, scale = _leaf8_pack(blob, depth)
-                if blob_nan is not None:
-                    blob_nan, _, _ = _leaf8_pack(blob_nan, depth, scale)
-                self.epi_args["a"] = self.epi_args.get("a", 1.0) * scale
-                self.variant = 2
-            self.variant |= nan_flags
-            self.rec_words = rec
-            wide = self.variant & 3 in (1, 2)
-            dyn = False
-            if wide:
-                # one 1024-thread workgroup per row tile: [G][rows] partials + feature plane(s) + two
-                # chunk buffers; tiles with missing values use the NaN blob with two planes
-                G = 1024 // self.rows_wide
-                plane = Fs * stride * 4
-                dyn = self.mode == 0 and self.rows_wide == 256  # MODE_SUM batch slots (csrc DYN / NPART)
-                npart = DYN_SLOTS if dyn else G
-                fixed = plane + (self.rows_wide + 4 + 8) * 4 + npart * self.rows_wide * 4
-                per_chunk = min((156 * 1024 - fixed) // 2, 64 * 1024)
-            else:
-                plane = F * TB * 4
-                fixed = plane + (TB + 4) * 4 + (self.C * TB * 4 if self.general else 0)
-                budget = max(lds_budget - fixed, 2 * rec * 4)  # two chunk buffers (double buffering)
-                per_chunk = min(budget // 2, 32 * 1024)  # register prefetch holds <= 32 KiB per chunk
-            if rec * 4 > per_chunk:
-                raise NotLowerable(f"depth-{depth} tree record ({rec * 4} B) exceeds the chunk buffer")
-            cap = DYN_B * DYN_SLOTS if wide and dyn else 0  # dynamic batches: one slot per batch
-            self.chunk_trees = self._chunk(per_chunk // (rec * 4), wide, max_chunk_trees, cap)
-            self.blob_nan, self.chunk_trees_nan = None, 0
-            if blob_nan is not None:
-                per_nan = min((156 * 1024 - fixed - plane) // 2, 64 * 1024)
-                if rec * 4 <= per_nan:
-                    self.chunk_trees_nan = self._chunk(per_nan // (rec * 4), wide, max_chunk_trees, cap)
-                    self.blob_nan = self._t(blob_nan.reshape(-1).view(np.int32))
-                else:
-                    self.variant &= ~(VAR_NAN_FAST | VAR_NAN_PLANES)
-            self.blob = self._t(blob.reshape(-1).view(np.int32))
-            self.roots = self.leaves = None
+            has_dr = self._lower_general(compiled, spec, opt)
         else:
-            if precision == "fp8":
-                raise NotLowerable("fp8 leaves need the PERFECT layout")
-            from .hybrid import head_words, pack_compact_bfs, pack_hybrid_compact, pack_super, pack_trees
-
-            feat_lds = F <= 64
-            H = 0
-            heads = None
-            if self.layout == "hybrid":
-                # PERFECT head of the top H levels in LDS + COMPACT depth-first tail from L2
-                # (tree_hybrid.hip); H = 4 measured best at depth 14 (profiles/r3c: larger heads
-                # pay more for the per-workgroup head copy and LDS bank conflicts than they save)
-                H = head_depth or 4
-                if H not in ((2, 3, 4) if hybrid_tail == "wide" else (4, 6, 8, 10)):
-                    raise ValueError("head_depth must be 4, 6, 8 or 10 (compact tail) or 2-4 (wide tail)")
-                fixed = (F * TB * 4 if feat_lds else 0) + TB * 4 + (self.C * TB * 4 if self.general else 0)
-                fit = (lds_budget - fixed) // (head_words(H) * 4)
-                if fit < 1:
-                    raise NotLowerable("no LDS left for a hybrid head chunk")
-                # small chunks: the head buffer must not cost occupancy (the tail walk hides L2 latency
-                # with waves; profiles/r3e: 234-tree chunks -> 2 workgroups per CU, 1.5x slower)
-                self.chunk_trees = int(min(fit, self.n_trees, max_chunk_trees or 32))
-                if hybrid_tail == "wide":
-                    heads, nodes, leaves, roots, has_dr = pack_trees(spec.trees, spec.weights, spec.P, H, feat_lds)
-                    self.tail_format = 2 if pointer_load == "uskip" else 1
-                else:
-                    try:
-                        heads, nodes, leaves, has_dr = pack_hybrid_compact(spec.trees, spec.weights, spec.P, H, F)
-                        roots = np.zeros(self.n_trees, dtype=np.int32)
-                        if leaves is None:
-                            leaves = np.zeros((1, 1), np.float32)
-                    except ValueError:
-                        self.layout, H, heads, self.chunk_trees = "pointer", 0, None, 0
+            # wide kernel geometry: stage only the columns the trees read (+ columns whose preparation
+            # can reject a row); row tiles of 256 / 128 / 64 rows keep the feature planes <= 64 KiB
+            stage = self._stage_columns(compiled, spec.trees)
+            rows = next((r for r, lim in ((256, 64), (128, 128), (64, 256)) if len(stage) <= lim), None)
+            wide_ok = (spec.P == 1 and depth <= 10 and rows is not None and opt.variant != "narrow"
+                       and (spec.mode == "sum" or spec.C <= 8))
+            if layout == "auto":
+                NI, NL = (1 << depth) - 1, 1 << depth
+                rec_bytes = 4 * (2 * NI + NL * spec.P + (NI + 31) // 32)
+                # deeper trees: the POINTER walk (profiles/r3q: 300 trees x depth 14, pointer 3.39 /
+                # 2.60 ms vs hybrid-head 4.55 / 3.11 ms for the forest / GBDT)
+                layout = "perfect" if depth <= 10 and (wide_ok or F <= 64) and rec_bytes <= 32 * 1024 else "pointer"
+            if spec.mode != "sum" and not (layout == "perfect" and wide_ok):
+                # votes / class slots accumulate in LDS on the narrow kernels (+ constant stumps
+                # carrying the per-class intercepts)
+                spec = to_general(spec)
+            self._adopt(spec, layout, spec.P > 1 or (spec.mode == "sum" and spec.slots is not None))
+            self.mode = {"sum": 0, "slot": 1, "class": 2}[spec.mode]
+            if layout == "perfect":
+                has_dr = self._lower_perfect(compiled, opt, stage, rows, wide_ok)
             else:
-                self.chunk_trees = 0
-            compact = superl = rank3 = False
-            if node_format == "rank3":
-                if heads is not None or not feat_lds or pointer_schedule != "lockstep" or F > 32:
-                    raise NotLowerable("rank3 pointer layout needs <= 32 features in LDS and the lock-step walk")
-                from .hybrid import pack_rank3
-
-                try:
-                    nodes, leaves, roots, rthr, rcnt, has_dr = pack_rank3(spec.trees, spec.weights, spec.P, F)
-                except ValueError as e:
-                    raise NotLowerable(f"rank3 pointer layout: {e}") from e
-                rank3 = True
-                self.rank_thr, self.rank_cnt = self._t(rthr.reshape(-1)), self._t(rcnt)
-                self.rank_stride = int(rthr.shape[1])
-                if leaves is None:
-                    leaves = np.zeros((1, 1), np.float32)
-            elif node_format == "super":
-                if heads is not None or not feat_lds or pointer_schedule != "lockstep" or F > 32:
-                    raise NotLowerable("super pointer layout needs <= 32 features in LDS and the lock-step walk")
-                try:
-                    nodes, leaves, roots, has_dr = pack_super(spec.trees, spec.weights, spec.P)
-                    roots = roots.view(np.int32)
-                    superl = True
-                    if leaves is None:
-                        leaves = np.zeros((1, 1), np.float32)
-                except ValueError as e:
-                    raise NotLowerable(f"super pointer layout: {e}") from e
-            elif heads is None and feat_lds and pointer_schedule == "lockstep" and node_format != "wide" \
-                    and node_order == "bfs":
-                try:
-                    nodes, leaves, roots, has_dr = pack_compact_bfs(spec.trees, spec.weights, spec.P)
-                    compact = True
-                    if leaves is None:
-                        leaves = np.zeros((1, 1), np.float32)
-                except ValueError:
-                    if node_format in ("compact", "lds"):
-                        raise NotLowerable(f"{node_format} pointer layout does not apply")
-                if compact and node_format == "lds":
-                    self._lds_chunks(nodes, roots, F, spec)
-            elif node_format == "compact":
-                raise NotLowerable("compact pointer layout needs features in LDS, lock-step, bfs")
-            inline = False
-            if heads is None and not compact and not superl and not rank3:
-                # inline leaf payloads on the default lock-step walk (sums, or unit votes) unless
-                # asked for the leaf table (pointer_leaf="table")
-                inline = (pointer_leaf == "inline" and self.layout == "pointer" and pointer_schedule == "lockstep"
-                          and pointer_load in ("clamped", "ltop") and pointer_ilp == 8
-                          and ((spec.P == 1 and spec.slots is None) or spec.P > 1))
-                _, nodes, leaves, roots, has_dr = pack_trees(spec.trees, spec.weights, spec.P, 0, feat_lds,
-                                                             order=node_order, inline_leaves=inline)
-            self.blob_nan, self.chunk_trees_nan = None, 0
-            self.head_depth = H
-            self.rec_words = head_words(H) if H else 0
-            # pointer walks: refill schedule (each PILP slot restarts on the next tree as soon as
-            # its walk ends) unless pinned to the lock-step kernel's tree-order sums
-            self.variant = VAR_POINTER_REFILL if (self.layout == "pointer" and pointer_schedule == "refill") else 0
-            if rank3:
-                self.variant = VAR_POINTER_RANK3
-            elif superl:
-                self.variant = VAR_POINTER_SUPER
-            elif compact and getattr(self, "lds_chunks", None) is not None:
-                self.variant = VAR_POINTER_LDS
-            elif compact:
-                self.variant = VAR_POINTER_COMPACT
-            elif pointer_load == "masked" and self.layout == "pointer" and self.variant == 0 and feat_lds:
-                self.variant = VAR_POINTER_MASKED  # finished walks skip their node load (exec mask)
-            elif pointer_load == "peel" and self.layout == "pointer" and self.variant == 0 and feat_lds:
-                self.variant = VAR_POINTER_PEEL  # top two levels from wave-uniform scalar loads
-            elif (pointer_load == "ltop" and self.layout == "pointer" and self.variant == 0 and feat_lds
-                  and node_order == "bfs" and pointer_ilp in (6, 8)):
-                self.variant = VAR_POINTER_LTOP | (VAR_POINTER_INLINE if inline else 0)  # levels 0-4 from LDS
-                # staging reads root + 0 .. 30 of every tree: pad so the last tree's stay in bounds
-                nodes = np.concatenate([nodes, np.zeros((POINTER_LTOP_NODES, 4), dtype=nodes.dtype)])
-            elif pointer_load == "uskip" and self.layout == "pointer" and self.variant == 0 and feat_lds:
-                self.variant = VAR_POINTER_USKIP  # slots finished in the whole wave issue no load
-            elif inline and self.variant == 0:
-                self.variant = VAR_POINTER_INLINE  # leaf payloads inline: no leaf gather
-            self.blob = self._t(nodes.reshape(-1).view(np.int32))
-            self.leaf_onehot = 0
-            if (self.general and self.P > 1 and leaves.size and self.layout == "pointer"
-                    and (self.variant in (0, VAR_POINTER_MASKED, VAR_POINTER_USKIP, VAR_POINTER_PEEL, VAR_POINTER_LTOP))):
-                # votes: every leaf row has at most one non-zero payload -> {class, weight} pairs
-                # (pointer_walk reads one 8-byte pair and updates one slot instead of P)
-                L = np.asarray(leaves, dtype=np.float32).reshape(len(leaves), -1)
-                nz = L != 0
-                if (nz.sum(axis=1) <= 1).all():
-                    cls = np.where(nz.any(axis=1), nz.argmax(axis=1), 0).astype(np.int32)
-                    w = L[np.arange(len(L)), cls].astype(np.float32)
-                    leaves = np.stack([cls, w.view(np.int32)], axis=1).view(np.float32)
-                    self.leaf_onehot = 1
-            self.leaves = self._t(leaves.reshape(-1))
-            self.roots = self._t(roots)
-            self.heads = self._t(heads.reshape(-1).view(np.int32)) if heads is not None else None
-            if xcd_split == "on":
-                self.xcd_split = XCD_SLICES
+                has_dr = self._lower_pointer(compiled, opt)
+        spec = self.spec
         if not (self.variant & 3):
             self.mode = 0  # narrow / pointer kernels: plain sums or LDS slot accumulators
         self.has_dr = has_dr
-        self.table = self._t(_label_table(spec.labels)) if spec.labels is not None else None
+        if spec.labels is not None:
+            self.table = self._t(_label_table(spec.labels))
         if self.general or self.mode == 1:
             sl = spec.slots if spec.slots is not None else [0] * self.n_trees
             self.slots = self._t(np.asarray(sl, dtype=np.int32))
-        else:
-            self.slots = None
-        self.splits = 1 if self.mode else splits
-        self._partial = None
+        self.splits = 1 if self.mode or self.layout == "general" else splits
+        self._post_state()
 
-    LDS_SLICES = 8  # XCD slices of the LDS-resident walk (one per XCD: tree_lds.hip)
+    def _adopt(self, spec: "EnsembleSpec", layout: str, general: bool) -> None:
+        """The ensemble in the form its layout scores, and the sizes every launch reads."""
+        self.spec, self.layout = spec, layout
+        self.n_trees, self.P, self.C = len(spec.trees), spec.P, spec.C
+        self.general = 1 if general else 0
+
+    # -- GENERAL layout (predicate VM over non-binary trees)
+    def _lower_general(self, compiled, spec, opt) -> bool:
+        if opt.precision == "fp8":
+            raise NotLowerable("fp8 leaves need the PERFECT layout")
+        from .general_tree import pack_general
+
+        if spec.mode == "slot" and any(b != 0.0 for b in (spec.acc_init or [])):
+            raise NotLowerable("K-class chains with intercepts over non-binary trees are host-only")
+        spec = to_general(spec)
+        self._adopt(spec, "general", spec.P > 1)
+        g = pack_general(spec.trees, spec.weights, spec.P, compiled.schema)
+        self.blob, self.children = self._t(g["nodes"].reshape(-1)), self._t(g["children"])
+        self.preds, self.pool = self._t(g["preds"].reshape(-1)), self._t(g["pool"])
+        self.trees_tab, self.leaves = self._t(g["trees"].reshape(-1)), self._t(g["payload"].reshape(-1))
+        if g["mix_mass"] is not None:
+            self.mix_mass, self.mix_w = self._t(g["mix_mass"].reshape(-1)), self._t(g["mix_w"])
+            self.mix_tab, self.mix_remap = self._t(g["mix_tab"].reshape(-1)), self._t(g["remap"])
+        if g["vcol"] is not None:
+            self.vcol = self._t(g["vcol"])
+        self.max_steps = g["max_steps"]
+        return False
+
+    # -- PERFECT layout (narrow and wide kernels)
+    def _lower_perfect(self, compiled, opt, stage, rows, wide_ok: bool) -> bool:
+        spec, depth, F = self.spec, self.depth, compiled.n_features
+        self.variant = int(opt.variant == "wide" or (opt.variant == "auto" and not self.general and wide_ok))
+        if self.variant == 1:
+            if not wide_ok:
+                raise NotLowerable("the wide tree kernel needs P = 1 and <= 256 staged columns")
+            self.rows_wide, self.n_stage = rows, len(stage)
+            stride = rows  # [F][rows] planes: traversal reads hit bank row mod 32 (csrc WideGeom)
+            fmap = {f: j for j, f in enumerate(stage)}
+            if stage != list(range(F)):
+                self.feat_map = self._t(np.array(stage, dtype=np.int32))
+        else:
+            if F > 64:
+                raise NotLowerable("the narrow perfect kernel stages at most 64 features")
+            stride, fmap = TB, None
+        leaf_bits = None
+        if spec.mode == "class":
+            self.mode = self._vote_mode(spec, rows)
+            if self.mode == 3:  # VOTE8: packed u8 counters, the leaf is the increment 1 << 8*class
+                leaf_bits = "vote8"
+            elif spec.tree_w is not None and any(w != 1.0 for w in spec.tree_w):
+                self.tree_w = self._t(np.asarray(spec.tree_w, np.float32))
+        if spec.mode == "slot" and spec.acc_init is not None and any(b != 0.0 for b in spec.acc_init):
+            self.acc_init = self._t(np.asarray(spec.acc_init, np.float32))
+        blob, rec, has_dr = _perfect_pack(spec.trees, spec.weights, spec.P, depth, stride=stride, fmap=fmap,
+                                          leaf_bits=leaf_bits)
+        Fs = self.n_stage
+        nan_flags, blob_nan = 0, None
+        if self.variant == 1 and opt.nan_mode == "auto" and not any(t.null_missing for t in spec.trees):
+            if not has_dr:
+                nan_flags = VAR_NAN_FAST
+            elif opt.precision != "fp8" or (2 * Fs - 1) * stride * 4 < (1 << 16):  # fp8 metas: 16-bit offsets
+                blob_nan = _nan_planes(blob, depth, Fs, stride)
+                nan_flags = VAR_NAN_FAST | VAR_NAN_PLANES
+        blob, blob_nan, rec = self._leaf_metas(opt.precision, blob, blob_nan, rec, Fs, stride)
+        self.variant |= nan_flags
+        self.rec_words = rec
+        wide = self.variant & 3 in (1, 2)
+        per_chunk, per_nan, cap = self._perfect_lds(wide, Fs, stride, rec, opt.lds_budget)
+        if rec * 4 > per_chunk:
+            raise NotLowerable(f"depth-{depth} tree record ({rec * 4} B) exceeds the chunk buffer")
+        self.chunk_trees = self._chunk(per_chunk // (rec * 4), wide, opt.max_chunk_trees, cap)
+        if blob_nan is not None:
+            if rec * 4 <= per_nan:
+                self.chunk_trees_nan = self._chunk(per_nan // (rec * 4), wide, opt.max_chunk_trees, cap)
+                self.blob_nan = self._t(blob_nan.reshape(-1).view(np.int32))
+            else:
+                self.variant &= ~(VAR_NAN_FAST | VAR_NAN_PLANES)
+        self.blob = self._t(blob.reshape(-1).view(np.int32))
+        return has_dr
+
+    def _leaf_metas(self, precision: str, blob, blob_nan, rec: int, Fs: int, stride: int):
+        """The wide kernel's records with the leaves folded into the last-level metas, where that
+        applies (``variant`` 2): VOTE8 class codes, or e4m3 leaf pairs under ``precision="fp8"``."""
+        spec, depth = self.spec, self.depth
+        if self.variant == 1 and self.mode == 3 and precision != "fp8" and depth >= 2 \
+                and (Fs * 2 if blob_nan is not None else Fs) * stride * 4 <= (1 << 16):
+            # VOTE8 forest: class codes in the last-level metas (no leaf array, no leaf read)
+            blob, rec = _vote_codes_pack(blob, depth)
+            if blob_nan is not None:
+                blob_nan, _ = _vote_codes_pack(blob_nan, depth)
+            self.variant = 2
+        if precision == "fp8":
+            # e4m3 leaves in the last-level metas, global scale folded into the epilogue
+            if self.general or self.variant != 1 or spec.mode != "sum":
+                raise NotLowerable("fp8 leaves need the single-accumulator wide kernel (P = 1)")
+            if (Fs - 1) * stride * 4 >= (1 << 16):
+                raise NotLowerable("fp8 leaf pairs need feature offsets below 64 KiB")
+            blob, rec, scale = _leaf8_pack(blob, depth)
+            if blob_nan is not None:
+                blob_nan, _, _ = _leaf8_pack(blob_nan, depth, scale)
+            self.epi_args["a"] = self.epi_args.get("a", 1.0) * scale
+            self.variant = 2
+        return blob, blob_nan, rec
+
+    def _perfect_lds(self, wide: bool, Fs: int, stride: int, rec: int, lds_budget: int) -> Tuple[int, int, int]:
+        """LDS bytes of one chunk buffer, of one on tiles with missing values (the NaN blob's second
+        feature plane takes its share; wide kernel only), and the wide kernel's tree cap per chunk."""
+        plane = Fs * stride * 4
+        if not wide:
+            fixed = plane + (TB + 4) * 4 + (self.C * TB * 4 if self.general else 0)
+            budget = max(lds_budget - fixed, 2 * rec * 4)  # two chunk buffers (double buffering)
+            return min(budget // 2, 32 * 1024), 0, 0  # register prefetch holds <= 32 KiB per chunk
+        # one 1024-thread workgroup per row tile: [G][rows] partials + feature plane(s) + two
+        # chunk buffers; tiles with missing values use the NaN blob with two planes
+        G = 1024 // self.rows_wide
+        dyn = self.mode == 0 and self.rows_wide == 256  # MODE_SUM batch slots (csrc DYN / NPART)
+        npart = DYN_SLOTS if dyn else G
+        fixed = plane + (self.rows_wide + 4 + 8) * 4 + npart * self.rows_wide * 4
+        cap = DYN_B * DYN_SLOTS if dyn else 0  # dynamic batches: one slot per batch
+        return min((156 * 1024 - fixed) // 2, 64 * 1024), min((156 * 1024 - fixed - plane) // 2, 64 * 1024), cap
+
+    # -- pointer and hybrid layouts
+    def _lower_pointer(self, compiled, opt) -> bool:
+        if opt.precision == "fp8":
+            raise NotLowerable("fp8 leaves need the PERFECT layout")
+        from .hybrid import head_words
+
+        F = compiled.n_features
+        feat_lds = F <= 64
+        H, heads, packed = (self._pack_hybrid(opt, F, feat_lds) if self.layout == "hybrid" else None) or (0, None, None)
+        fmt, inline, own = self._pack_nodes(opt, F, feat_lds, heads is not None)
+        nodes, leaves, roots, has_dr = own or packed
+        if leaves is None:
+            leaves = np.zeros((1, 1), np.float32)
+        self.head_depth, self.rec_words = H, head_words(H) if H else 0
+        self.variant = _pointer_variant(self.layout, opt.pointer_schedule, opt.pointer_load, opt.node_order,
+                                        opt.pointer_ilp, feat_lds, fmt, inline)
+        if self.variant & VAR_POINTER_LTOP:
+            # staging reads root + 0 .. 30 of every tree: pad so the last tree's stay in bounds
+            nodes = np.concatenate([nodes, np.zeros((POINTER_LTOP_NODES, 4), dtype=nodes.dtype)])
+        self.blob = self._t(nodes.reshape(-1).view(np.int32))
+        if (self.general and self.P > 1 and leaves.size and self.layout == "pointer"
+                and (self.variant in (0, VAR_POINTER_MASKED, VAR_POINTER_USKIP, VAR_POINTER_PEEL, VAR_POINTER_LTOP))):
+            pairs = _onehot_leaf_pairs(leaves)
+            if pairs is not None:
+                leaves, self.leaf_onehot = pairs, 1
+        self.leaves = self._t(leaves.reshape(-1))
+        self.roots = self._t(roots)
+        self.heads = self._t(heads.reshape(-1).view(np.int32)) if heads is not None else None
+        if opt.xcd_split == "on":
+            self.xcd_split = XCD_SLICES
+        return has_dr
+
+    def _pack_hybrid(self, opt, F: int, feat_lds: bool):
+        """PERFECT head of the top H levels in LDS + a tail walked from L2 (tree_hybrid.hip): ``(H,
+        heads, (nodes, leaves, roots, has_dr))``, or None when the compact tail cannot hold the forest
+        (the plan falls back to the pointer layout). H = 4 measured best at depth 14 (profiles/r3c:
+        larger heads pay more for the per-workgroup head copy and LDS bank conflicts than they save)."""
+        from .hybrid import head_words, pack_hybrid_compact, pack_trees
+
+        spec = self.spec
+        H = opt.head_depth or 4
+        if H not in ((2, 3, 4) if opt.hybrid_tail == "wide" else (4, 6, 8, 10)):
+            raise ValueError("head_depth must be 4, 6, 8 or 10 (compact tail) or 2-4 (wide tail)")
+        fixed = (F * TB * 4 if feat_lds else 0) + TB * 4 + (self.C * TB * 4 if self.general else 0)
+        fit = (opt.lds_budget - fixed) // (head_words(H) * 4)
+        if fit < 1:
+            raise NotLowerable("no LDS left for a hybrid head chunk")
+        # small chunks: the head buffer must not cost occupancy (the tail walk hides L2 latency
+        # with waves; profiles/r3e: 234-tree chunks -> 2 workgroups per CU, 1.5x slower)
+        self.chunk_trees = int(min(fit, self.n_trees, opt.max_chunk_trees or 32))
+        if opt.hybrid_tail == "wide":
+            heads, *tail = pack_trees(spec.trees, spec.weights, spec.P, H, feat_lds)
+            self.tail_format = 2 if opt.pointer_load == "uskip" else 1
+            return H, heads, tuple(tail)
+        try:
+            heads, nodes, leaves, has_dr = pack_hybrid_compact(spec.trees, spec.weights, spec.P, H, F)
+        except ValueError:
+            self.layout, self.chunk_trees = "pointer", 0
+            return None
+        return H, heads, (nodes, leaves, np.zeros(self.n_trees, dtype=np.int32), has_dr)
+
+    def _pack_nodes(self, opt, F: int, feat_lds: bool, hybrid: bool):
+        """Pointer nodes in the asked ``node_format``: ``(format, inline, (nodes, leaves, roots,
+        has_dr))`` with format ``"rank3"`` / ``"super"`` / ``"compact"`` / ``"lds"`` or None (16-byte
+        nodes). A hybrid plan's tail is packed already: only the refusals apply (arrays None)."""
+        from .hybrid import pack_compact_bfs, pack_rank3, pack_super, pack_trees
+
+        spec, fmt = self.spec, opt.node_format
+        lockstep = opt.pointer_schedule == "lockstep"
+        if fmt in ("rank3", "super"):
+            if hybrid or not feat_lds or not lockstep or F > 32:
+                raise NotLowerable(f"{fmt} pointer layout needs <= 32 features in LDS and the lock-step walk")
+            try:
+                if fmt == "rank3":
+                    nodes, leaves, roots, rthr, rcnt, has_dr = pack_rank3(spec.trees, spec.weights, spec.P, F)
+                else:
+                    nodes, leaves, roots, has_dr = pack_super(spec.trees, spec.weights, spec.P)
+                    roots = roots.view(np.int32)
+            except ValueError as e:
+                raise NotLowerable(f"{fmt} pointer layout: {e}") from e
+            if fmt == "rank3":
+                self.rank_thr, self.rank_cnt = self._t(rthr.reshape(-1)), self._t(rcnt)
+                self.rank_stride = int(rthr.shape[1])
+            return fmt, False, (nodes, leaves, roots, has_dr)
+        if not hybrid and feat_lds and lockstep and fmt != "wide" and opt.node_order == "bfs":
+            try:
+                packed = pack_compact_bfs(spec.trees, spec.weights, spec.P)
+            except ValueError:
+                if fmt in ("compact", "lds"):
+                    raise NotLowerable(f"{fmt} pointer layout does not apply")
+                packed = None
+            if packed is not None:
+                if fmt == "lds":
+                    self._lds_chunks(packed[0], packed[2], F, spec)
+                return ("lds" if fmt == "lds" else "compact"), False, tuple(packed)
+        elif fmt == "compact":
+            raise NotLowerable("compact pointer layout needs features in LDS, lock-step, bfs")
+        if hybrid:
+            return None, False, None
+        # inline leaf payloads on the default lock-step walk (sums, or unit votes) unless
+        # asked for the leaf table (pointer_leaf="table")
+        inline = (opt.pointer_leaf == "inline" and self.layout == "pointer" and lockstep
+                  and opt.pointer_load in ("clamped", "ltop") and opt.pointer_ilp == 8
+                  and ((spec.P == 1 and spec.slots is None) or spec.P > 1))
+        _, nodes, leaves, roots, has_dr = pack_trees(spec.trees, spec.weights, spec.P, 0, feat_lds,
+                                                     order=opt.node_order, inline_leaves=inline)
+        return None, inline, (nodes, leaves, roots, has_dr)
 
     def _lds_chunks(self, nodes, roots, F: int, spec) -> None:
         """Chunk tables of ``node_format="lds"`` (``tree_lds.hip``): 512-row tiles (256 when the
         feature planes leave too little room), the rest of the 160 KiB LDS one chunk buffer."""
         from .hybrid import pack_lds_chunks
 
-        general = spec.P > 1 or (spec.mode == "sum" and spec.slots is not None)
-        CA = spec.C if general else 1
-        if general and (spec.C > 8 or spec.P > 8):
+        CA = spec.C if self.general else 1
+        if self.general and (spec.C > 8 or spec.P > 8):
             raise NotLowerable("lds pointer layout: at most 8 class slots")
         last = None
         for rows in (512, 256):
@@ -1800,20 +1823,13 @@ class TreePlan(DevicePlan):
     def _launch_lds(self, a, n: int, stream) -> None:
         import ctypes
 
-        import torch
-
         from ..ops._lib import LdsTreeArgs, check, ptr, stream_handle
 
         S = int(self.lds_n_slices)
         a.partial = None
         if S > 1:
             CA = self.C if self.general else 1
-            need = S * (CA + 1) * n
-            if self._partial is None or self._partial.numel() < need:
-                if self._partial is not None:
-                    self.__dict__.setdefault("_retired", []).append(self._partial)
-                self._partial = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=self.device)
-            a.partial = ptr(self._partial)
+            a.partial = self._shared_partial(S * (CA + 1) * n)
         la = LdsTreeArgs()
         la.t = a
         la.chunks, la.slice_chunk = ptr(self.lds_chunks), ptr(self.lds_slices)
@@ -1853,7 +1869,7 @@ class TreePlan(DevicePlan):
         c = int(max(1, min(self.n_trees, fit)))
         if slot_cap:
             c = min(c, slot_cap)
-        G = 1024 // getattr(self, "rows_wide", 256)
+        G = 1024 // self.rows_wide
         if wide and c < self.n_trees:
             q = DYN_B if slot_cap else (8 * G if c >= 16 * G else 2 * G)
             c = max(q, c // q * q) if c >= q else c
@@ -1889,7 +1905,9 @@ class TreePlan(DevicePlan):
             raise NotLowerable(str(e)) from e
 
     def _post_state(self) -> None:
-        self._partial = None
+        """The launch-side caches of a plan whose state is complete (built or rebuilt)."""
+        self._partial = None  # split partials, shared by every launch (_shared_partial)
+        self._retired = []
         self._args = {}
         self._args_buf = {}
 
@@ -1900,7 +1918,7 @@ class TreePlan(DevicePlan):
 
         from ..ops._lib import TreeArgs, ptr
 
-        cache = self.__dict__.setdefault("_args", {})
+        cache = self._args
         a = cache.get(with_probs)
         if a is None:
             a = TreeArgs()
@@ -1908,21 +1926,17 @@ class TreePlan(DevicePlan):
             a.blob, a.roots, a.leaves, a.tree_slot = ptr(self.blob), ptr(self.roots), ptr(self.leaves), ptr(self.slots)
             a.n_trees, a.rec_words, a.chunk_trees, a.P = self.n_trees, self.rec_words, self.chunk_trees, self.P
             a.C, a.general, a.variant = self.C, self.general, self.variant
-            a.blob_nan, a.chunk_trees_nan = ptr(getattr(self, "blob_nan", None)), getattr(self, "chunk_trees_nan", 0)
-            a.tree_w, a.acc_init = ptr(getattr(self, "tree_w", None)), ptr(getattr(self, "acc_init", None))
-            a.feat_map = ptr(getattr(self, "feat_map", None))
-            a.rows_wide, a.mode = getattr(self, "rows_wide", TB), getattr(self, "mode", 0)
-            a.n_stage = getattr(self, "n_stage", self.n_features)
-            a.pilp = getattr(self, "pointer_ilp", 8)
-            a.prof = ptr(getattr(self, "prof", None))  # kbench --tree-prof phase timers (nullable)
-            a.rank_thr, a.rank_cnt = ptr(getattr(self, "rank_thr", None)), ptr(getattr(self, "rank_cnt", None))
-            a.rank_stride = int(getattr(self, "rank_stride", 0) or 0)
-            a.leaf_onehot = int(getattr(self, "leaf_onehot", 0) or 0)
+            a.blob_nan, a.chunk_trees_nan = ptr(self.blob_nan), self.chunk_trees_nan
+            a.tree_w, a.acc_init, a.feat_map = ptr(self.tree_w), ptr(self.acc_init), ptr(self.feat_map)
+            a.rows_wide, a.mode, a.n_stage, a.pilp = self.rows_wide, self.mode, self.n_stage, self.pointer_ilp
+            a.prof = ptr(self.prof)  # kbench --tree-prof phase timers (nullable)
+            a.rank_thr, a.rank_cnt, a.rank_stride = ptr(self.rank_thr), ptr(self.rank_cnt), int(self.rank_stride)
+            a.leaf_onehot = int(self.leaf_onehot)
             a.epi = _epilogue(table=self.table, write_probs=with_probs, **self.epi_args)
             cache[with_probs] = a
         # one mutable copy per thread, reused across launches: the C launcher copies the struct
-        # before returning, and every per-launch field is rewritten by launch()
-        bufs = self.__dict__.setdefault("_args_buf", {})
+        # before returning, and every per-launch field is rewritten by _bind_rows()
+        bufs = self._args_buf
         key = (threading.get_ident(), with_probs)
         b = bufs.get(key)
         if b is None:
@@ -1936,7 +1950,7 @@ class TreePlan(DevicePlan):
         if self.splits:
             return self.splits
         blocks = (n_rows + TB - 1) // TB
-        if getattr(self, "xcd_split", 0) and self.n_trees >= 2 * XCD_SLICES:
+        if self.xcd_split and self.n_trees >= 2 * XCD_SLICES:
             return XCD_SLICES
         if self.layout == "perfect" and self.variant & 3 and self.n_trees >= 64:
             # wide kernel (one 1024-thread workgroup per 256-row tile): about one workgroup per CU
@@ -1950,40 +1964,51 @@ class TreePlan(DevicePlan):
 
     supports_direct = True  # epilogue can write straight into zero-copy host memory (+ mirror)
 
+    def _bind_rows(self, a, x_ptr, n: int, n_feat: int, ldx: int, score, valid, s: int = 1, row_valid=None,
+                   probs=None, score2=None, valid2=None) -> None:
+        """Write the per-launch half of a ``TreeArgs`` (addresses, or None for NULL): the rows, where
+        their results go, no split partials yet, and whether ``s`` tree slices go to the XCDs."""
+        a.X, a.n_rows, a.n_feat, a.ldx = x_ptr, n, n_feat, ldx
+        a.row_valid_in = row_valid
+        a.score, a.valid, a.probs = score, valid, probs
+        a.epi.score2, a.epi.valid2 = score2, valid2
+        a.partial = None
+        a.xcd_split = 1 if self.xcd_split and s > 1 else 0
+
+    def _shared_partial(self, need: int) -> int:
+        """Address of the plan's split-partial buffer, grown to hold ``need`` floats."""
+        if self._partial is None or self._partial.numel() < need:
+            import torch
+
+            if self._partial is not None:
+                # an in-flight kernel on another stream may still use it: never hand it back
+                self._retired.append(self._partial)
+            self._partial = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=self.device)
+        return self._partial.data_ptr()
+
     def launch(self, X, score, valid, stream=None, probs=None, row_valid=None, splits: Optional[int] = None,
                score2=None, valid2=None) -> None:
         import ctypes
 
-        import torch
-
-        from ..ops._lib import TreeArgs, check, ptr, stream_handle
+        from ..ops._lib import check, ptr, stream_handle
 
         n = X.shape[0]
         if X.shape[1] == 0:
             # feature-less trees (single leaves, e.g. a chain segment with an empty MiningSchema):
             # the kernels still stage one column, so hand them a real one instead of a 0-wide
             # tensor whose data pointer owns no bytes
+            import torch
+
             X = torch.zeros((n, 1), dtype=torch.float32, device=X.device)
         if self.layout == "general":
             self._launch_general(X, score, valid, stream, probs, row_valid, score2, valid2)
             return
         s = splits if splits is not None else self._auto_splits(n)
         a = self._args_template(probs is not None)
-        a.X = X.data_ptr()
-        a.n_rows, a.n_feat, a.ldx = n, X.shape[1], X.stride(0)
-        a.row_valid_in = ptr(row_valid)
-        a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
-        a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
-        a.partial = None
-        a.xcd_split = 1 if getattr(self, "xcd_split", 0) and s > 1 else 0
+        self._bind_rows(a, X.data_ptr(), n, X.shape[1], X.stride(0), _addr(score), _addr(valid), s, ptr(row_valid),
+                        ptr(probs), _addr(score2), _addr(valid2))
         if s > 1:
-            need = s * (self.C + 1) * n
-            if self._partial is None or self._partial.numel() < need:
-                if self._partial is not None:
-                    # an in-flight kernel on another stream may still use it: never hand it back
-                    self.__dict__.setdefault("_retired", []).append(self._partial)
-                self._partial = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=self.device)
-            a.partial = ptr(self._partial)
+            a.partial = self._shared_partial(s * (self.C + 1) * n)
         if self.variant & VAR_POINTER_LDS:
             self._launch_lds(a, n, stream)
             return
@@ -1992,15 +2017,13 @@ class TreePlan(DevicePlan):
 
             h = HybridArgs()
             h.t = a
-            h.heads, h.head_words = ptr(self.heads), int(self.rec_words)
-            h.tail_format = int(getattr(self, "tail_format", 0))
+            h.heads, h.head_words, h.tail_format = ptr(self.heads), int(self.rec_words), int(self.tail_format)
             rc = self.lib.pmml_tree_hybrid_launch(stream_handle(stream), ctypes.byref(h), int(self.head_depth), s)
             check(rc, f"tree kernel (hybrid, head {self.head_depth}, depth {self.depth})")
             return
         rc = self.lib.pmml_tree_launch(stream_handle(stream), ctypes.byref(a), 0 if self.layout == "perfect" else 1,
                                        self.depth, 1 if self.has_dr else 0, s)
         check(rc, f"tree kernel ({self.layout}, depth {self.depth})")
-
 
     def row_launcher(self, X, score, valid):
         """A launch of this plan over FIXED buffers (``StreamingScorer.score_row``'s persistent
@@ -2019,15 +2042,9 @@ class TreePlan(DevicePlan):
         s = self._auto_splits(n)
         a = TreeArgs()
         ctypes.memmove(ctypes.byref(a), ctypes.byref(self._args_template(False)), ctypes.sizeof(TreeArgs))
-        a.X = X.data_ptr()
-        a.n_rows, a.n_feat, a.ldx = n, X.shape[1], X.stride(0)
-        a.row_valid_in = None
-        a.score, a.valid, a.probs = _addr(score), _addr(valid), None
-        a.epi.score2, a.epi.valid2 = None, None
-        a.partial = None
-        a.xcd_split = 1 if getattr(self, "xcd_split", 0) and s > 1 else 0
+        self._bind_rows(a, X.data_ptr(), n, X.shape[1], X.stride(0), _addr(score), _addr(valid), s)
         partial = None
-        if s > 1:
+        if s > 1:  # its own, exactly sized: bound for the life of the closure
             partial = torch.empty(max(s * (self.C + 1) * n, 1), dtype=torch.float32, device=self.device)
             a.partial = partial.data_ptr()
         lib, layout = self.lib, 0 if self.layout == "perfect" else 1
@@ -2044,27 +2061,15 @@ class TreePlan(DevicePlan):
         """``(TreeArgs, (layout, depth, has_dr, splits))`` of one launch over rows at ``x_ptr``,
         for ``pmml_tree_launch_many`` (several models' launches from one host call), or ``None``
         when this plan launches otherwise (hybrid / general layouts go through :meth:`launch`)."""
-        import torch
-
-        from ..ops._lib import TreeArgs, ptr
+        from ..ops._lib import TreeArgs
 
         if self.layout not in ("perfect", "pointer") or n <= 0 or self.variant & VAR_POINTER_LDS:
             return None
         s = self._auto_splits(n)
         a = TreeArgs.from_buffer_copy(self._args_template(False))
-        a.X, a.n_rows, a.n_feat, a.ldx = x_ptr, n, n_feat, ldx
-        a.row_valid_in = None
-        a.score, a.valid, a.probs = score_ptr, valid_ptr, None
-        a.epi.score2, a.epi.valid2 = None, None
-        a.partial = None
-        a.xcd_split = 1 if getattr(self, "xcd_split", 0) and s > 1 else 0
+        self._bind_rows(a, x_ptr, n, n_feat, ldx, score_ptr, valid_ptr, s)
         if s > 1:
-            need = s * (self.C + 1) * n
-            if self._partial is None or self._partial.numel() < need:
-                if self._partial is not None:
-                    self.__dict__.setdefault("_retired", []).append(self._partial)
-                self._partial = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=self.device)
-            a.partial = ptr(self._partial)
+            a.partial = self._shared_partial(s * (self.C + 1) * n)
         return a, (0 if self.layout == "perfect" else 1, int(self.depth), 1 if self.has_dr else 0, int(s))
 
     def grouped_args(self, n_feat: int):
@@ -2074,8 +2079,7 @@ class TreePlan(DevicePlan):
         Entries with equal ``key`` share one launch; the row fields are set on the device."""
         from ..ops._lib import TreeArgs
 
-        if self.layout != "perfect" or not (self.variant & 3) or self.P != 1 or \
-                getattr(self, "n_stage", self.n_features) > n_feat:
+        if self.layout != "perfect" or not (self.variant & 3) or self.P != 1 or self.n_stage > n_feat:
             return None
         a = TreeArgs.from_buffer_copy(self._args_template(False))
         a.X, a.n_rows, a.n_feat, a.ldx = None, 0, n_feat, n_feat
@@ -2092,17 +2096,12 @@ class TreePlan(DevicePlan):
 
         g = GenTreeArgs()
         g.t = self._args_template(probs is not None)
-        g.t.X = X.data_ptr()
-        g.t.n_rows, g.t.n_feat, g.t.ldx = X.shape[0], X.shape[1], X.stride(0)
-        g.t.row_valid_in = ptr(row_valid)
-        g.t.score, g.t.valid, g.t.probs = _addr(score), _addr(valid), ptr(probs)
-        g.t.epi.score2, g.t.epi.valid2 = _addr(score2), _addr(valid2)
-        g.t.partial = None
+        self._bind_rows(g.t, X.data_ptr(), X.shape[0], X.shape[1], X.stride(0), _addr(score), _addr(valid), 1,
+                        ptr(row_valid), ptr(probs), _addr(score2), _addr(valid2))
         g.nodes, g.children, g.preds = ptr(self.blob), ptr(self.children), ptr(self.preds)
         g.pool, g.trees, g.max_steps = ptr(self.pool), ptr(self.trees_tab), int(self.max_steps)
-        g.mix_mass, g.mix_w = ptr(getattr(self, "mix_mass", None)), ptr(getattr(self, "mix_w", None))
-        g.mix_tab, g.remap = ptr(getattr(self, "mix_tab", None)), ptr(getattr(self, "mix_remap", None))
-        g.vcol = ptr(getattr(self, "vcol", None))
+        g.mix_mass, g.mix_w = ptr(self.mix_mass), ptr(self.mix_w)
+        g.mix_tab, g.remap, g.vcol = ptr(self.mix_tab), ptr(self.mix_remap), ptr(self.vcol)
         check(self.lib.pmml_tree_general_launch(stream_handle(stream), ctypes.byref(g)), "general tree kernel")
 
 

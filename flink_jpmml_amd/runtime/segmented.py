@@ -202,7 +202,8 @@ def _index_outputs(plan) -> None:
     """Make a classification segment plan emit class *indices* (its epilogue's label table off)."""
     if getattr(plan, "table", None) is not None:
         plan.table = None
-        plan.__dict__.pop("_args", None)
+        if "_args" in plan.__dict__:
+            plan._args = {}  # a TreePlan's cached argument blocks hold the table's address
     inner = getattr(plan, "inner", None)
     if inner is not None:
         _index_outputs(inner)
