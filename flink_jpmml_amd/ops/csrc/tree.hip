@@ -1,6 +1,6 @@
 // Tree-ensemble scoring: POINTER / GENERAL layouts, split reduction and the C entry points.
 // The PERFECT-layout kernels live in tree_common.h (one translation unit per depth: tree_d<D>.hip).
-#include "tree_common.h"
+#include "tree_walk.h"
 
 namespace pmml_tree {
 namespace {
@@ -1116,182 +1116,75 @@ PMML_API int pmml_tree_launch(hipStream_t stream, const TreeArgs* args, int layo
     size_t lds = (feat_lds ? (size_t)a.n_feat * TB * 4 : 0) + TB * 4 + acc_lds;
     // pointer_walk kernels (PEEL / USKIP / INLINE / default): feature planes + accumulators only
     const size_t lds_pw = (feat_lds ? (size_t)a.n_feat * TB * 4 : 0) + acc_lds;
+    // every branch below: variant -> its checks -> one launch (kernel, LDS bytes)
+    auto go = [&](auto kernel, size_t bytes) { return launch_k(kernel, grid, dim3(TB), bytes, stream, a); };
+    const bool g = a.general != 0;
     if (a.variant == VAR_POINTER_RANK3) {
       if (a.n_feat > 32 || !a.rank_thr || !a.rank_cnt || a.rank_stride < 1 || a.rank_stride > 254) return -4;
       // (ranks replace the feature planes; the threshold tables are read from global memory)
       if (lds > 160 * 1024) return -5;
-      if (a.general) {
-        err = prepare_launch(tree_rank3_kernel<true>, lds);
-        if (!err) hipLaunchKernelGGL((tree_rank3_kernel<true>), grid, dim3(TB), lds, stream, a);
-      } else if (a.pilp == 16) {
-        err = prepare_launch(tree_rank3_kernel<false, 16>, lds);
-        if (!err) hipLaunchKernelGGL((tree_rank3_kernel<false, 16>), grid, dim3(TB), lds, stream, a);
-      } else if (a.pilp == 4) {
-        err = prepare_launch(tree_rank3_kernel<false, 4>, lds);
-        if (!err) hipLaunchKernelGGL((tree_rank3_kernel<false, 4>), grid, dim3(TB), lds, stream, a);
-      } else {
-        err = prepare_launch(tree_rank3_kernel<false>, lds);
-        if (!err) hipLaunchKernelGGL((tree_rank3_kernel<false>), grid, dim3(TB), lds, stream, a);
-      }
+      err = g             ? go(tree_rank3_kernel<true>, lds)
+          : a.pilp == 16 ? go(tree_rank3_kernel<false, 16>, lds)
+          : a.pilp == 4  ? go(tree_rank3_kernel<false, 4>, lds)
+                         : go(tree_rank3_kernel<false>, lds);
     } else if (a.variant == VAR_POINTER_SUPER) {
       if (a.n_feat > 32) return -4;  // 5-bit feature fields
-      if (a.general) {
-        err = prepare_launch(tree_super_kernel<true>, lds);
-        if (!err) hipLaunchKernelGGL((tree_super_kernel<true>), grid, dim3(TB), lds, stream, a);
-      } else if (a.pilp == 16) {
-        err = prepare_launch(tree_super_kernel<false, 16>, lds);
-        if (!err) hipLaunchKernelGGL((tree_super_kernel<false, 16>), grid, dim3(TB), lds, stream, a);
-      } else if (a.pilp == 4) {
-        err = prepare_launch(tree_super_kernel<false, 4>, lds);
-        if (!err) hipLaunchKernelGGL((tree_super_kernel<false, 4>), grid, dim3(TB), lds, stream, a);
-      } else if (a.pilp == 2) {
-        err = prepare_launch(tree_super_kernel<false, 2>, lds);
-        if (!err) hipLaunchKernelGGL((tree_super_kernel<false, 2>), grid, dim3(TB), lds, stream, a);
-      } else {
-        err = prepare_launch(tree_super_kernel<false>, lds);
-        if (!err) hipLaunchKernelGGL((tree_super_kernel<false>), grid, dim3(TB), lds, stream, a);
-      }
+      err = g             ? go(tree_super_kernel<true>, lds)
+          : a.pilp == 16 ? go(tree_super_kernel<false, 16>, lds)
+          : a.pilp == 4  ? go(tree_super_kernel<false, 4>, lds)
+          : a.pilp == 2  ? go(tree_super_kernel<false, 2>, lds)
+                         : go(tree_super_kernel<false>, lds);
     } else if (a.variant == VAR_POINTER_COMPACT) {
       if (!feat_lds) return -4;
-      if (a.general) {
-        err = prepare_launch(tree_compact_kernel<true>, lds);
-        if (!err) hipLaunchKernelGGL((tree_compact_kernel<true>), grid, dim3(TB), lds, stream, a);
-      } else {
-        err = prepare_launch(tree_compact_kernel<false>, lds);
-        if (!err) hipLaunchKernelGGL((tree_compact_kernel<false>), grid, dim3(TB), lds, stream, a);
-      }
+      err = g ? go(tree_compact_kernel<true>, lds) : go(tree_compact_kernel<false>, lds);
     } else if (a.variant == VAR_POINTER_REFILL) {
       lds += (size_t)REFILL_ROOTS_LDS * 4;
-      if (a.general) {
-        if (feat_lds) {
-          err = prepare_launch(tree_pointer_refill_kernel<true, true>, lds);
-          if (!err) hipLaunchKernelGGL((tree_pointer_refill_kernel<true, true>), grid, dim3(TB), lds, stream, a);
-        } else {
-          err = prepare_launch(tree_pointer_refill_kernel<true, false>, lds);
-          if (!err) hipLaunchKernelGGL((tree_pointer_refill_kernel<true, false>), grid, dim3(TB), lds, stream, a);
-        }
-      } else {
-        if (feat_lds) {
-          err = prepare_launch(tree_pointer_refill_kernel<false, true>, lds);
-          if (!err) hipLaunchKernelGGL((tree_pointer_refill_kernel<false, true>), grid, dim3(TB), lds, stream, a);
-        } else {
-          err = prepare_launch(tree_pointer_refill_kernel<false, false>, lds);
-          if (!err) hipLaunchKernelGGL((tree_pointer_refill_kernel<false, false>), grid, dim3(TB), lds, stream, a);
-        }
-      }
+      err = dispatch_bool(g, [&](auto G) {
+        return dispatch_bool(feat_lds, [&](auto L) {
+          return go(tree_pointer_refill_kernel<decltype(G)::value, decltype(L)::value>, lds);
+        });
+      });
     } else if (a.variant == (VAR_POINTER_LTOP | VAR_POINTER_INLINE) && feat_lds) {
       const size_t lt = lds_pw + (size_t)8 * 31 * 16;
-      if (a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, false, false, false, true, 5, 1>, lt);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, false, false, false, true, 5, 1>), grid, dim3(TB), lt,
-                             stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, false, false, false, true, 5, 1>, lt);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, false, false, false, true, 5, 1>), grid, dim3(TB), lt,
-                             stream, a);
-      }
+      err = g ? go(tree_pointer_kernel<true, true, 8, false, false, false, true, 5, 1>, lt)
+              : go(tree_pointer_kernel<false, true, 8, false, false, false, true, 5, 1>, lt);
     } else if (a.variant == VAR_POINTER_LTOP && feat_lds) {
       // levels 0-4 (31 nodes a tree), one LDS buffer (profiles/r6l: two buffers or a sixth level
       // cost a workgroup per CU and measured no faster for sums, 16-20 % slower for votes)
       const size_t lt = lds_pw + (size_t)(a.pilp == 6 ? 6 : 8) * 31 * 16;
-      if (a.pilp == 6) {
-        if (a.general) {
-          err = prepare_launch(tree_pointer_kernel<true, true, 6, false, false, false, false, 5, 1>, lt);
-          if (!err)
-            hipLaunchKernelGGL((tree_pointer_kernel<true, true, 6, false, false, false, false, 5, 1>), grid, dim3(TB),
-                               lt, stream, a);
-        } else {
-          err = prepare_launch(tree_pointer_kernel<false, true, 6, false, false, false, false, 5, 1>, lt);
-          if (!err)
-            hipLaunchKernelGGL((tree_pointer_kernel<false, true, 6, false, false, false, false, 5, 1>), grid, dim3(TB),
-                               lt, stream, a);
-        }
-      } else if (a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, false, false, false, false, 5, 1>, lt);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, false, false, false, false, 5, 1>), grid, dim3(TB), lt,
-                             stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, false, false, false, false, 5, 1>, lt);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, false, false, false, false, 5, 1>), grid, dim3(TB), lt,
-                             stream, a);
-      }
+      if (a.pilp == 6)
+        err = g ? go(tree_pointer_kernel<true, true, 6, false, false, false, false, 5, 1>, lt)
+                : go(tree_pointer_kernel<false, true, 6, false, false, false, false, 5, 1>, lt);
+      else
+        err = g ? go(tree_pointer_kernel<true, true, 8, false, false, false, false, 5, 1>, lt)
+                : go(tree_pointer_kernel<false, true, 8, false, false, false, false, 5, 1>, lt);
     } else if (a.variant == VAR_POINTER_PEEL && feat_lds) {
-      if (a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, false, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, false, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      }
+      err = g ? go(tree_pointer_kernel<true, true, 8, false, false, true>, lds_pw)
+              : go(tree_pointer_kernel<false, true, 8, false, false, true>, lds_pw);
     } else if (a.variant == VAR_POINTER_USKIP && feat_lds) {
-      if (a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (a.pilp == 4) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 4, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 4, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (a.pilp == 16) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 16, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 16, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      }
+      err = g             ? go(tree_pointer_kernel<true, true, 8, false, true>, lds_pw)
+          : a.pilp == 4  ? go(tree_pointer_kernel<false, true, 4, false, true>, lds_pw)
+          : a.pilp == 16 ? go(tree_pointer_kernel<false, true, 16, false, true>, lds_pw)
+                         : go(tree_pointer_kernel<false, true, 8, false, true>, lds_pw);
     } else if (a.variant == VAR_POINTER_INLINE) {
-      if (feat_lds && a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, false, false, false, true>, lds_pw);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, false, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, false, false, false, true>, lds_pw);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, false, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (a.general) {
-        err = prepare_launch(tree_pointer_kernel<true, false, 8, false, false, false, true>, lds_pw);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<true, false, 8, false, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, false, 8, false, false, false, true>, lds_pw);
-        if (!err)
-          hipLaunchKernelGGL((tree_pointer_kernel<false, false, 8, false, false, false, true>), grid, dim3(TB), lds_pw, stream, a);
-      }
+      err = dispatch_bool(g, [&](auto G) {
+        return dispatch_bool(feat_lds, [&](auto L) {
+          return go(tree_pointer_kernel<decltype(G)::value, decltype(L)::value, 8, false, false, false, true>, lds_pw);
+        });
+      });
     } else if (a.variant == VAR_POINTER_USKIP || a.variant == VAR_POINTER_PEEL || a.variant == VAR_POINTER_LTOP) {
       return -4;  // features in LDS only
-    } else if (a.general) {
-      if (feat_lds && (a.variant & VAR_POINTER_MASKED)) {
-        err = prepare_launch(tree_pointer_kernel<true, true, 8, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<true, true, 8, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds) {
-        err = prepare_launch(tree_pointer_kernel<true, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<true, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<true, false>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<true, false>), grid, dim3(TB), lds_pw, stream, a);
-      }
+    } else if (!feat_lds) {
+      err = g ? go(tree_pointer_kernel<true, false>, lds_pw) : go(tree_pointer_kernel<false, false>, lds_pw);
+    } else if (g) {
+      err = (a.variant & VAR_POINTER_MASKED) ? go(tree_pointer_kernel<true, true, 8, true>, lds_pw)
+                                             : go(tree_pointer_kernel<true, true>, lds_pw);
     } else {
-      if (feat_lds && a.pilp == 2) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 2>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 2>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds && (a.variant & VAR_POINTER_MASKED)) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 8, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 8, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds && a.pilp == 16) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 16>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 16>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds && a.pilp == 4) {
-        err = prepare_launch(tree_pointer_kernel<false, true, 4>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true, 4>), grid, dim3(TB), lds_pw, stream, a);
-      } else if (feat_lds) {
-        err = prepare_launch(tree_pointer_kernel<false, true>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, true>), grid, dim3(TB), lds_pw, stream, a);
-      } else {
-        err = prepare_launch(tree_pointer_kernel<false, false>, lds_pw);
-        if (!err) hipLaunchKernelGGL((tree_pointer_kernel<false, false>), grid, dim3(TB), lds_pw, stream, a);
-      }
+      err = a.pilp == 2                      ? go(tree_pointer_kernel<false, true, 2>, lds_pw)
+          : (a.variant & VAR_POINTER_MASKED) ? go(tree_pointer_kernel<false, true, 8, true>, lds_pw)
+          : a.pilp == 16                     ? go(tree_pointer_kernel<false, true, 16>, lds_pw)
+          : a.pilp == 4                      ? go(tree_pointer_kernel<false, true, 4>, lds_pw)
+                                             : go(tree_pointer_kernel<false, true>, lds_pw);
     }
   }
   if (err) return err;
@@ -1396,24 +1289,11 @@ PMML_API int pmml_tree_general_launch(hipStream_t stream, const GenTreeArgs* arg
   const bool feat_lds = a.n_feat <= 64;
   const size_t acc_lds = a.general ? (size_t)a.C * TB * 4 : 0;
   const size_t lds = (feat_lds ? (size_t)a.n_feat * TB * 4 : 0) + TB * 4 + acc_lds;
-  int err = 0;
-  if (a.general) {
-    if (feat_lds) {
-      err = prepare_launch(tree_general_kernel<true, true>, lds);
-      if (!err) hipLaunchKernelGGL((tree_general_kernel<true, true>), grid, dim3(TB), lds, stream, ga);
-    } else {
-      err = prepare_launch(tree_general_kernel<true, false>, lds);
-      if (!err) hipLaunchKernelGGL((tree_general_kernel<true, false>), grid, dim3(TB), lds, stream, ga);
-    }
-  } else {
-    if (feat_lds) {
-      err = prepare_launch(tree_general_kernel<false, true>, lds);
-      if (!err) hipLaunchKernelGGL((tree_general_kernel<false, true>), grid, dim3(TB), lds, stream, ga);
-    } else {
-      err = prepare_launch(tree_general_kernel<false, false>, lds);
-      if (!err) hipLaunchKernelGGL((tree_general_kernel<false, false>), grid, dim3(TB), lds, stream, ga);
-    }
-  }
+  const int err = dispatch_bool(a.general != 0, [&](auto G) {
+    return dispatch_bool(feat_lds, [&](auto L) {
+      return launch_k(tree_general_kernel<decltype(G)::value, decltype(L)::value>, grid, dim3(TB), lds, stream, ga);
+    });
+  });
   if (err) return err;
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
@@ -1429,14 +1309,9 @@ PMML_API int pmml_tree_pointer_multi(hipStream_t stream, const MultiTreeArgs* ar
     return -4;
   const size_t lds = (size_t)m.n_feat * TB * 4 + TB * 4 + (general ? (size_t)max_C * TB * 4 : 0);
   const dim3 grid((m.n_rows + TB - 1) / TB, 1, m.count);
-  int err;
-  if (general) {
-    err = prepare_launch(tree_pointer_multi_kernel<true>, lds);
-    if (!err) hipLaunchKernelGGL((tree_pointer_multi_kernel<true>), grid, dim3(TB), lds, stream, m);
-  } else {
-    err = prepare_launch(tree_pointer_multi_kernel<false>, lds);
-    if (!err) hipLaunchKernelGGL((tree_pointer_multi_kernel<false>), grid, dim3(TB), lds, stream, m);
-  }
+  const int err = dispatch_bool(general != 0, [&](auto G) {
+    return launch_k(tree_pointer_multi_kernel<decltype(G)::value>, grid, dim3(TB), lds, stream, m);
+  });
   if (err) return err;
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }

@@ -25,7 +25,7 @@
 // bits 30/31 as in the head (runtime/hybrid.py packs both). A walk stops at its leaf's parent and
 // the leaves of the 8 lock-step trees are read together afterwards: no serial extra round trip.
 // Epilogue, slots and split mode are the pointer kernel's.
-#include "tree_common.h"
+#include "tree_walk.h"
 
 namespace pmml_tree {
 namespace {
@@ -182,6 +182,8 @@ __global__ __launch_bounds__(TB, 2) void tree_hybrid_kernel(HybridArgs ha) {
           else
             for (int p = 0; p < a.P; ++p) accl[(slot + p) * TB + tid] += a.leaves[(size_t)val[i] * a.P + p];
         } else if (a.P > 1) {
+          // unreachable: every P > 1 plan is GENERAL (runtime/plans.py, TreePlan._adopt). Kept: deleting
+          // it alone moves the VGPR counts of five kernels (profiles/tree_walk_helpers.md).
           acc += a.leaves[(size_t)val[i] * a.P];
         } else {
           acc += __uint_as_float(val[i]);
@@ -336,61 +338,34 @@ __global__ __launch_bounds__(TB, 2) void tree_hybrid_ptr_kernel(HybridArgs ha) {
   finish_row(a, acc, accl, blk.y, GENERAL, row, row_ok && !poisoned);
 }
 
-// Split-mode reduction (same partial layout as the pointer kernel).
-__global__ __launch_bounds__(TB) void tree_hybrid_reduce_kernel(TreeArgs a, int splits) {
-  const int row = blockIdx.x * TB + threadIdx.x;
-  if (row >= a.n_rows) return;
-  const size_t stride = (size_t)a.n_rows;
-  float acc[16];
-  const int C = a.C;
-  for (int c = 0; c < 16; ++c) acc[c] = 0.f;
-  bool ok = true;
-  for (int s = 0; s < splits; ++s) {
-    const float* base = a.partial + (size_t)s * (C + 1) * stride;
-    for (int c = 0; c < C && c < 16; ++c) acc[c] += base[c * stride + row];
-    ok = ok && base[C * stride + row] == 0.f;
-  }
-  apply_epilogue(a.epi, [&](int c) { return acc[c]; }, ok, row, a.n_rows, a.score, a.valid, a.probs);
-}
-
 template <bool GENERAL, bool FEAT_LDS, int H>
 int launch_hybrid_t(hipStream_t stream, const HybridArgs& ha, dim3 grid, size_t lds) {
+  auto go = [&](auto kernel) { return launch_k(kernel, grid, dim3(TB), lds, stream, ha); };
   if constexpr (H > 4) {
     if (ha.tail_format != 0) return -6;  // pointer tails: heads of 2-4 levels (profiles/r3ar)
   } else {
-  if (ha.tail_format == 1) {  // 16-byte pointer tail, clamped loads
-    int err = prepare_launch(tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, false>, lds);
-    if (err) return err;
-    hipLaunchKernelGGL((tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, false>), grid, dim3(TB), lds, stream, ha);
-    return 0;
+    // 16-byte pointer tail: 1 = clamped loads, 2 = wave-uniform skip of finished slots
+    if (ha.tail_format == 1) return go(tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, false>);
+    if (ha.tail_format == 2) return go(tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, true>);
   }
-  if (ha.tail_format == 2) {  // 16-byte pointer tail, wave-uniform skip of finished slots
-    int err = prepare_launch(tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, true>, lds);
-    if (err) return err;
-    hipLaunchKernelGGL((tree_hybrid_ptr_kernel<GENERAL, FEAT_LDS, H, true>), grid, dim3(TB), lds, stream, ha);
-    return 0;
-  }
-  }
-  int err = prepare_launch(tree_hybrid_kernel<GENERAL, FEAT_LDS, H>, lds);
-  if (err) return err;
-  hipLaunchKernelGGL((tree_hybrid_kernel<GENERAL, FEAT_LDS, H>), grid, dim3(TB), lds, stream, ha);
-  return 0;
+  return go(tree_hybrid_kernel<GENERAL, FEAT_LDS, H>);
 }
 
 template <int H>
 int launch_hybrid_h(hipStream_t stream, const HybridArgs& ha, dim3 grid, size_t lds, bool general, bool feat_lds) {
-  if (general) {
-    return feat_lds ? launch_hybrid_t<true, true, H>(stream, ha, grid, lds)
-                    : launch_hybrid_t<true, false, H>(stream, ha, grid, lds);
-  }
-  return feat_lds ? launch_hybrid_t<false, true, H>(stream, ha, grid, lds)
-                  : launch_hybrid_t<false, false, H>(stream, ha, grid, lds);
+  return dispatch_bool(general, [&](auto G) {
+    return dispatch_bool(feat_lds, [&](auto L) {
+      return launch_hybrid_t<decltype(G)::value, decltype(L)::value, H>(stream, ha, grid, lds);
+    });
+  });
 }
 
 }  // namespace
 }  // namespace pmml_tree
 
 using namespace pmml_tree;
+
+PMML_API int pmml_tree_reduce(hipStream_t stream, const TreeArgs* args, int splits);  // tree.hip
 
 PMML_API int pmml_tree_hybrid_args_size() { return (int)sizeof(HybridArgs); }
 
@@ -432,10 +407,6 @@ PMML_API int pmml_tree_hybrid_launch(hipStream_t stream, const HybridArgs* args,
   }
   if (err) return err;
   if (hipGetLastError() != hipSuccess) return -7;
-  if (splits > 1) {
-    dim3 g2((a.n_rows + TB - 1) / TB);
-    hipLaunchKernelGGL(tree_hybrid_reduce_kernel, g2, dim3(TB), 0, stream, a, splits);
-    if (hipGetLastError() != hipSuccess) return -8;
-  }
+  if (splits > 1) return pmml_tree_reduce(stream, &a, splits);
   return 0;
 }

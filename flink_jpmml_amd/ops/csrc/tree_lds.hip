@@ -26,7 +26,7 @@
 // tree-order sum of the pointer kernel: results agree to fp32 rounding, the oracle check is the
 // contract). Votes / class slots (GENERAL): per-thread register accumulators, C <= 8.
 
-#include "tree_common.h"
+#include "tree_walk.h"
 
 namespace pmml_tree {
 namespace {
@@ -261,10 +261,7 @@ __global__ __launch_bounds__(LT, 1) void tree_lds_kernel(LdsTreeArgs la) {
 
 template <bool GENERAL, int ROWS>
 int launch_lds(hipStream_t st, const LdsTreeArgs& la, dim3 grid, size_t lds) {
-  auto k = tree_lds_kernel<GENERAL, ROWS>;
-  int err = prepare_launch(k, lds);
-  if (!err) hipLaunchKernelGGL(k, grid, dim3(LT), lds, st, la);
-  return err;
+  return launch_k(tree_lds_kernel<GENERAL, ROWS>, grid, dim3(LT), lds, st, la);
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 leaves, see tests/_boundary.py), vote labels equal, no row excluded.
 
 Shapes: 2049 rows (a ragged last tile and a 1-row tile), 19 trees (one full and one partial 16-walk
-group), F = 8 (40 for the wide PERFECT kernel), depth 5 for PERFECT and 9 for the pointer family
+group), F = 8 (40 for the wide PERFECT kernel, 65 where the walk kernels leave the features in
+global memory), depth 5 for PERFECT and 9 for the pointer family
 (past the 5 LDS-staged LTOP levels, the hybrid head and the rank3 / super multi-level records).
 Each tree of a document takes another mutant (operator pair, child order, fp32 / decimal
 thresholds), and every cell of the input is a split constant +-2 ulps or a special value."""
@@ -96,9 +97,32 @@ PATHS = [
     ("perfect-splits4", 5, 8, dict(layout="perfect", variant="narrow"), dict(splits=4), BOTH, 0),
     ("pointer-splits4", 9, 8, dict(layout="pointer"), dict(splits=4), BOTH, 0),
 ]
+# PATHS above is also the grid tests/test_tree_plan_pins.py pins against its recorded fixture, so
+# it only grows together with that fixture; the rows below run through the same two tests here.
+MORE_PATHS = [
+    # F = 65: features stay in global memory (the walk kernels' lazy per-read preparation)
+    ("pointer-clamped-f65", 9, 65, dict(layout="pointer", pointer_load="clamped"), {}, BOTH, 0),
+    ("pointer-refill-f65", 9, 65, dict(layout="pointer", pointer_schedule="refill"), {}, BOTH, PL.VAR_POINTER_REFILL),
+    ("pointer-inline-f65", 9, 65, dict(layout="pointer", pointer_leaf="inline"), {}, BOTH, PL.VAR_POINTER_INLINE),
+    ("hybrid-compact-tail-f65", 9, 65, dict(layout="hybrid", hybrid_tail="compact"), {}, BOTH, 0),
+    ("hybrid-wide-tail-f65", 9, 65, dict(layout="hybrid", hybrid_tail="wide"), {}, BOTH, 0),
+    ("general-f65", 5, 65, dict(layout="general"), {}, BOTH, 0),
+    # split partials of the other node formats (pointer-splits4 covers the plain pointer walk)
+    ("pointer-compact-splits4", 9, 8, dict(layout="pointer", node_format="compact"), dict(splits=4), BOTH,
+     PL.VAR_POINTER_COMPACT),
+    ("pointer-super-splits4", 9, 8, dict(layout="pointer", node_format="super"), dict(splits=4), BOTH,
+     PL.VAR_POINTER_SUPER),
+    ("pointer-rank3-splits4", 9, 8, dict(layout="pointer", node_format="rank3"), dict(splits=4), BOTH,
+     PL.VAR_POINTER_RANK3),
+    ("pointer-refill-splits4", 9, 8, dict(layout="pointer", pointer_schedule="refill"), dict(splits=4), BOTH,
+     PL.VAR_POINTER_REFILL),
+    ("hybrid-compact-tail-splits4", 9, 8, dict(layout="hybrid", hybrid_tail="compact"), dict(splits=4), BOTH, 0),
+    ("hybrid-wide-tail-splits4", 9, 8, dict(layout="hybrid", hybrid_tail="wide"), dict(splits=4), BOTH, 0),
+]
 MISSING = ["defaultChild", "nullPrediction"]
-NO_NULL = {"pointer-rank3"}  # the rank3 records carry no null-on-missing flag: refused at lowering
-CASES = [(p, m) for p in PATHS for m in MISSING if not (m == "nullPrediction" and p[0] in NO_NULL)]
+ALL_PATHS = PATHS + MORE_PATHS
+NO_NULL = {"pointer-rank3", "pointer-rank3-splits4"}  # the rank3 records carry no null-on-missing flag: refused at lowering
+CASES = [(p, m) for p in ALL_PATHS for m in MISSING if not (m == "nullPrediction" and p[0] in NO_NULL)]
 
 
 def _lowers(c, opts):
@@ -109,7 +133,7 @@ def _lowers(c, opts):
         return None
 
 
-@pytest.mark.parametrize("path", PATHS, ids=[p[0] for p in PATHS])
+@pytest.mark.parametrize("path", ALL_PATHS, ids=[p[0] for p in ALL_PATHS])
 def test_every_kernel_path_lowers_as_named(path):
     """CPU: each case's options select the kernel it is named after (no silent other path), for
     both models under both missing-value strategies."""
@@ -130,6 +154,22 @@ def test_every_kernel_path_lowers_as_named(path):
             assert plan.variant & 3 == 0
         if opts.get("xcd_split") == "on":
             assert plan.xcd_split == PL.XCD_SLICES and plan._auto_splits(ROWS) > 1
+        if F > 64:  # the kernels stage features in LDS up to 64 columns: these stay in global memory
+            assert plan.n_features == F
+            # what a node reads is then a column index below F, never an LDS byte offset (f * 1024)
+            u32 = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
+            if plan.layout == "pointer":
+                fields = u32(plan.blob).reshape(-1, 4)[:, 1] & 0xFFFF
+            elif plan.layout == "hybrid":
+                NI = (1 << plan.head_depth) - 1
+                fields = u32(plan.heads).reshape(plan.n_trees, plan.rec_words)[:, 1:2 * NI:2].reshape(-1) & 0xFFFF
+                wide = plan.tail_format != 0
+                tail = u32(plan.blob).reshape(-1, 4 if wide else 2)[:, 1] & (0xFFFF if wide else 0xFF)
+                fields = np.concatenate([fields, tail])
+            else:  # general: predicate rows {op | neg << 8, field, ..}; ops 3..7 read a field
+                preds = u32(plan.preds).reshape(-1, 4)
+                fields = preds[np.isin(preds[:, 0] & 0xFF, (3, 4, 5, 6, 7)), 1]
+            assert fields.size and 8 <= int(fields.max()) < F
 
 
 @pytest.mark.gpu
@@ -144,6 +184,100 @@ def test_kernel_path_on_boundary_inputs(gpu, path, missing):
         assert plan.variant & bits == bits
         s, v = _score(plan, X, **launch)
         _assert_same(s, v, ref, vref, f"{name} {model} {missing}")
+
+
+# ------------------------------------------------- leaf payloads of the lock-step pointer walk
+#
+# pointer_walk (tree.hip) adds a GENERAL leaf in one of four ways. Where the GPU suite reaches them
+# (plans traced through the whole suite):
+#   * one-hot {class, weight} pairs: every 3-class vote forest on the lock-step path, e.g.
+#     test_kernel_path_on_boundary_inputs[pointer-clamped / -masked / -uskip / -peel-dfs / -ltop];
+#   * runtime-P loop: P = 1 class slots, test_gpu_epilogue.py::test_tree_chain_epilogues[pointer-multiclass];
+#   * dense P == 3 gather: only behind inline leaves (pointer-inline rows, test_inline_leaves.py), where
+#     all but single-leaf trees skip it, and in members of segmented plans (test_gpu_segment_reduce.py);
+#   * dense P == 2 gather: nowhere.
+# The two dense gathers get the cases below: an `average` forest whose leaves carry integer class
+# payloads (ScoreDistribution probability = 0..6, not one-hot), 16 trees, so every class mean is a
+# sum of integers below 2**7 times 2**-4: exact in fp32 and in the float64 oracle alike.
+DENSE_TREES = 16
+DENSE_PATHS = [
+    ("clamped", dict(layout="pointer", pointer_load="clamped"), {}),
+    ("uskip", dict(layout="pointer", pointer_load="uskip"), {}),
+    ("splits4", dict(layout="pointer"), dict(splits=4)),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def dense_case(n_classes: int, missing: str):
+    """(compiled, X, oracle labels, validity, class means) of the integer-payload average forest."""
+    import re
+
+    from tests import _epilogue_cases as E
+
+    txt = random_forest_pmml(n_trees=DENSE_TREES, depth=9, n_features=8, n_classes=n_classes, seed=23, p_split=0.75)
+    txt = B.mix_mutants(txt).replace('multipleModelMethod="majorityVote"', 'multipleModelMethod="average"')
+    count = [0]
+
+    def leaf(m):
+        k = count[0]
+        count[0] += 1
+        dist = "".join(f'<ScoreDistribution value="{c}" recordCount="1" probability="{(k * (c + 2) + c) % 7}"/>'
+                       for c in range(n_classes))
+        return m.group(1) + m.group(2) + dist + m.group(3)
+
+    txt, n = re.subn(r'(<Node id="\d+" score="[^"]+">)(<SimplePredicate [^>]*/>)(</Node>)', leaf, txt)
+    assert n > DENSE_TREES
+    if missing == "nullPrediction":
+        txt = B.null_prediction(txt)
+    c = CompiledPmml.from_string(txt)
+    X = B.boundary_matrix(B.split_cuts(txt, 8), ROWS, seed=n_classes)
+    ref, vref, probs = E.oracle(c, X)
+    assert vref.any() and (missing == "defaultChild" or not vref.all())
+    sums = probs[vref] * DENSE_TREES
+    assert np.array_equal(sums, np.round(sums)) and sums.max() < 2 ** 7  # integer sums: fp32-exact means
+    assert (np.sort(sums, axis=1)[:, :-1] > 0).any()  # not one-hot: more than one class has mass
+    for a in (X, ref, vref, probs):
+        a.setflags(write=False)
+    return c, X, ref, vref, probs
+
+
+@pytest.mark.parametrize("n_classes", [3, 2])
+def test_dense_leaf_payloads_lower_to_the_dense_gathers(n_classes):
+    """CPU: the cases below take pointer_walk's dense ``P == 3`` / ``P == 2`` branch (GENERAL, P = the
+    class count, no one-hot pairs, the lock-step kernel)."""
+    for missing in MISSING:
+        c = dense_case(n_classes, missing)[0]
+        for name, opts, _ in DENSE_PATHS:
+            plan = _lowers(c, opts)
+            assert plan is not None and plan.layout == "pointer" and plan.general == 1, (name, missing)
+            assert plan.P == n_classes and plan.C == n_classes and not plan.leaf_onehot
+            # tree_pointer_kernel (pointer_walk) with the leaves in the leaf table, not inline
+            assert plan.variant in (0, PL.VAR_POINTER_USKIP, PL.VAR_POINTER_LTOP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("missing", MISSING)
+@pytest.mark.parametrize("n_classes", [3, 2])
+def test_dense_leaf_payloads_on_boundary_inputs(gpu, n_classes, missing):
+    """The dense gathers, bit for bit: every class mean equals the oracle's on every valid row,
+    validity exact, labels equal wherever the oracle's best class is not tied."""
+    c, X, ref, vref, probs = dense_case(n_classes, missing)
+    top = np.sort(probs[vref], axis=1)
+    clear = top[:, -1] > top[:, -2]
+    assert clear.sum() >= vref.sum() // 2
+    for name, opts, launch in DENSE_PATHS:
+        plan = PL.TreePlan(c, gpu, **opts)
+        assert plan.P == n_classes and not plan.leaf_onehot
+        Xt = torch.from_numpy(np.array(X, dtype=F32)).to(gpu)
+        s, v = plan.alloc_outputs(len(X))
+        p = torch.full((len(X), n_classes), -7.0, dtype=torch.float32, device=gpu)
+        plan.launch(Xt, s, v, probs=p, **launch)
+        torch.cuda.synchronize()
+        s, v, p = s.cpu().numpy(), v.cpu().numpy().astype(bool), p.cpu().numpy()
+        what = f"dense P = {n_classes} {name} {missing}"
+        assert np.array_equal(v, vref), f"{what}: validity differs on {(v != vref).sum()} rows"
+        assert np.array_equal(p[vref], probs[vref].astype(F32)), f"{what}: class means differ from the oracle"
+        assert np.array_equal(s[vref][clear].astype(F32), ref[vref][clear].astype(F32)), f"{what}: labels differ"
 
 
 @pytest.mark.gpu
