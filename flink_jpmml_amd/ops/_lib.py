@@ -216,7 +216,7 @@ class KnnArgs(ctypes.Structure):
 class GemmArgs(ctypes.Structure):
     _fields_ = [("A", c_void_p), ("Wt", c_void_p), ("bias", c_void_p), ("C", c_void_p), ("rows", c_int),
                 ("rows_p", c_int), ("K", c_int), ("Mp", c_int), ("lda", c_int), ("ldw", c_int), ("ldc", c_int),
-                ("act", c_int), ("thr", c_float), ("n_out", c_int), ("final_norm", c_int), ("f32", c_int),
+                ("act", c_int), ("thr", c_float), ("n_out", c_int), ("final_norm", c_int), ("flags", c_int),
                 ("row_ok", c_void_p), ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p),
                 ("probs", c_void_p)]
 
@@ -354,6 +354,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                                  ctypes.c_int, ctypes.c_int]
         lib.pmml_gemm_launch.restype = ctypes.c_int
         lib.pmml_gemm_launch.argtypes = [c_void_p, ctypes.POINTER(GemmArgs), ctypes.c_int]
+        lib.pmml_gemm_route.restype = ctypes.c_int
+        lib.pmml_gemm_route.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_int]
+        lib.pmml_gemm_fused_head_route.restype = ctypes.c_int
+        lib.pmml_gemm_fused_head_route.argtypes = [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmArgs)]
         lib.pmml_nn_decode_wide.restype = ctypes.c_int
         lib.pmml_nn_decode_wide.argtypes = [c_void_p, ctypes.POINTER(GemmArgs), c_void_p, c_int]
         lib.pmml_nn_first_layer_launch.restype = ctypes.c_int

@@ -28,17 +28,19 @@
 //   output activation, softmax / simplemax, label table or regression affine + Target stage and
 //   writes score / valid / probabilities (the zero-copy sink pointers of the pipeline).
 //
-// Which kernel takes a layer (pmml_gemm_launch / pmml_gemm_fused_head_launch):
-//   bf16 hidden, K = 64          gemm_k64p_kernel  persistent over row tiles, weights staged once,
+// Which kernel takes a layer (route() / route_fused_head(), as GemmKernel ids):
+//   bf16 hidden, K = 64          GK_K64P_NTS       persistent over row tiles, weights staged once,
 //                                                   non-temporal 128-byte row-segment stores
-//   bf16 hidden, K >= 128        gemm8p_kernel     persistent 256 x 256 phase-interleaved walk
+//   bf16 hidden, K >= 128        GK_G8P            persistent 256 x 256 phase-interleaved walk
 //                                                   (LDS-DMA slice stream across tiles, SADDR asm)
-//   last hidden + output layer   gemm8p_kernel<true> (n_out <= 4) / gemm8_kernel<true>: the output
-//                                                   layer folded into the accumulators, no H store
-//   output layer / fp32 / flags  gemm_kernel       the 2-buffer loop described above
-//   bit 12 (A/B reference)       gemm8_kernel / gemm_kernel, one tile per workgroup
-// Every alternative path stays selectable by a flag bit of GemmArgs.f32 and is pinned bit for bit
-// against the default by tests/test_wide_mlp.py.
+//   last hidden + output layer   GK_G8P_HEAD (n_out <= 4) / GK_G8_HEAD: the output layer folded
+//                                                   into the accumulators, no H store
+//   output layer                 GK_GEMM_HEAD / GK_GEMM_HEAD_F32   the 2-buffer loop described above
+//   fp32 hidden                  GK_GEMM_F32       the same loop on the fp32 MFMA
+//   GF_NO_P8 (A/B reference)     GK_G8_T (K >= 512) / GK_GEMM_T, one tile per workgroup
+// Every other id is an alternative path that stays selectable by a GemmFlag bit of GemmArgs.flags
+// and is pinned bit for bit against the default by tests/test_wide_mlp.py; the routing itself is
+// pinned by tests/test_gpu_gemm_route.py.
 #include "epilogue.h"
 #include "nn_act.h"
 
@@ -64,22 +66,33 @@ struct GemmArgs {
   int lda, ldw, ldc, act;
   float thr;              // threshold activation parameter
   int n_out, final_norm;  // output layer: real units, 0 none / 1 softmax / 2 simplemax
-  int f32;                // bit 0: operand / activation type (0 bf16, 1 fp32); experiment bits (A/B tests,
-                          // WideMlpPlan.gemm_flags): 5 wave-private LDS epilogue, 6 K = 64 on the 256 x 256
-                          // tile, 7 force the phase-interleaved kernel, 8 direct [row][unit] stores instead of
-                          // store_hidden_t, 9 one K = 64 tile per workgroup instead of gemm_k64p_kernel,
-                          // 10 gemm_k64p_kernel with store_hidden_t instead of the row-segment stores,
-                          // 11 the same for gemm8_kernel<false, true>, 12 one tile per workgroup
-                          // (gemm8_kernel) instead of the persistent gemm8p_kernel, 13 gemm8p_kernel
-                          // without its epilogue stores (timing only: the layer output is not written),
-                          // 14 gemm_k64p_kernel with ordinary instead of non-temporal stores, 15
-                          // gemm8p_kernel storing each tile in two halves (deferred, measured slower),
-                          // 16 gemm8p_kernel also above K = 1024 (experiment)
+  int flags;              // GemmFlag bits
   const uint8_t* row_ok;  // [rows] input-stage validity (output layer)
   Epilogue epi;           // output layer decode (affine + Target, or label table)
   float* score;
   uint8_t* valid;
   float* probs;
+};
+
+// GemmArgs.flags. Bit 0 is the operand type; bits 5 to 16 are experiment bits (A/B runs,
+// WideMlpPlan.gemm_flags): each keeps the path that a default replaced, or one measured and not
+// taken, selectable. route() reads them; unknown bits are rejected.
+enum GemmFlag {
+  GF_F32 = 1 << 0,            // fp32 operands and activations (clear: bf16)
+  GF_WAVE_EPI = 1 << 5,       // wave-private LDS epilogue of the direct stores (measured slower, profiles/r4k)
+  GF_K64_WIDE = 1 << 6,       // K = 64 on the 256 x 256 tile, not the 128-row K = 64 kernels (profiles/r4j)
+  GF_PH8 = 1 << 7,            // phase-interleaved kernels below K = 512 / K = 128 too (default above: profiles/r3ao)
+  GF_DIRECT = 1 << 8,         // direct [row][unit] stores instead of store_hidden_t (profiles/r4y, r4aa)
+  GF_K64_TILE = 1 << 9,       // one K = 64 tile per workgroup instead of gemm_k64p_kernel (profiles/r4y)
+  GF_K64P_T = 1 << 10,        // gemm_k64p_kernel with store_hidden_t instead of row-segment stores (profiles/r5g)
+  GF_PH8_T = 1 << 11,         // the same for gemm8_kernel<false, true>, which also keeps off gemm8p_kernel (profiles/r5g)
+  GF_NO_P8 = 1 << 12,         // one tile per workgroup instead of the persistent gemm8p_kernel (profiles/r5q, r5u)
+  GF_P8_NOSTORE = 1 << 13,    // gemm8p_kernel without epilogue stores: timing only, no layer output (profiles/r5q)
+  GF_K64P_TEMPORAL = 1 << 14, // gemm_k64p_kernel with ordinary instead of non-temporal stores (profiles/r5q)
+  GF_P8_DEFER = 1 << 15,      // gemm8p_kernel storing each tile in two halves (measured slower, profiles/r5q)
+  GF_P8_ANY = 1 << 16,        // gemm8p_kernel also past p8_fits() and GF_NO_P8 (experiment, profiles/r5u)
+  GF_ALL = GF_F32 | GF_WAVE_EPI | GF_K64_WIDE | GF_PH8 | GF_DIRECT | GF_K64_TILE | GF_K64P_T | GF_PH8_T | GF_NO_P8 |
+           GF_P8_NOSTORE | GF_K64P_TEMPORAL | GF_P8_DEFER | GF_P8_ANY,
 };
 
 struct PrepArgs {
@@ -292,7 +305,7 @@ __device__ __forceinline__ void store_hidden(const GemmArgs& a, const f32x16 (&a
 // dword pair trades runs between the lane halves so that every lane owns two whole 16-byte runs
 // (units 0-7 and 16-23 in the low half, 8-15 and 24-31 in the high half) and stores them straight
 // from the registers: 2 full-width stores per lane per 32 x 32 tile instead of 16 two-unit stores
-// by half the lanes, no LDS, no barrier. Default for the bf16 hidden kernels; flag bit 8 (0x100)
+// by half the lanes, no LDS, no barrier. Default for the bf16 hidden kernels; GF_DIRECT (0x100)
 // selects store_hidden.
 // LB: bl holds the column tile's 256 biases in LDS (16-byte reads) instead of a.bias.
 template <int ACT, int TM, int TN, bool LB>
@@ -482,7 +495,7 @@ __device__ __forceinline__ void decode_row(const GemmArgs& a, int row, const flo
   }
 }
 
-// Hidden-layer epilogue through a wave-private LDS scratch (bf16; opt-in, flag bit 5 — measured
+// Hidden-layer epilogue through a wave-private LDS scratch (bf16; opt-in, GF_WAVE_EPI — measured
 // slower than the direct stores: 2.70 vs 2.60 ms for a 1024 x 1024 layer, 0.99 vs 0.84 ms for the
 // K = 64 layer, profiles/r4k). Each 32 x 32 accumulator tile
 // (a unit per lane, 16 rows in the registers) is written to the wave's own 2.5 KiB of LDS as bf16
@@ -770,7 +783,7 @@ __global__ __launch_bounds__(K64_NT, 2) void gemm_k64_kernel(GemmArgs a, PrepArg
     store_hidden_t_any<TM, TN>(a, acc, row0, col0, wm, wn, lane);
     return;
   }
-  if ((a.f32 >> 5) & 1) {  // bit 5: the wave-private LDS epilogue (measured slower, profiles/r4k)
+  if (a.flags & GF_WAVE_EPI) {  // the wave-private LDS epilogue (measured slower, profiles/r4k)
     __syncthreads();  // every wave is done reading the staged tiles: their LDS becomes scratch
     store_hidden_wave_any<TM, TN>(a, acc, row0, col0, wm, wn, lane, smem + wave * WEPI_BYTES);
     return;
@@ -1058,15 +1071,15 @@ __global__ __launch_bounds__(NT, 1) void gemm8_kernel(GemmArgs a, HeadFuse hf) {
     }
     return;
   } else if constexpr (TST) {
-    if (!((a.f32 >> 11) & 1)) {
+    if (!(a.flags & GF_PH8_T)) {
       // 128-byte row-segment stores through a 2 KiB wave scratch (the staging slots are drained:
-      // every wave is past the balancing barrier above); bit 11: store_hidden_t
+      // every wave is past the balancing barrier above); GF_PH8_T: store_hidden_t
       store_hidden_seg_any<TM, TN, false>(a, acc, row0, col0, wr, wc, lane, nullptr, smem + wave * 2048);
     } else {
       store_hidden_t_any<TM, TN>(a, acc, row0, col0, wr, wc, lane);
     }
   } else {
-    if ((a.f32 >> 5) & 1) {  // bit 5: the wave-private LDS epilogue (measured slower, profiles/r4k)
+    if (a.flags & GF_WAVE_EPI) {  // the wave-private LDS epilogue (measured slower, profiles/r4k)
       // every wave is past its last LDS read of the staged slices (the balancing barrier above)
       store_hidden_wave_any<TM, TN>(a, acc, row0, col0, wr, wc, lane, smem + wave * WEPI_BYTES);
       return;
@@ -1082,7 +1095,7 @@ __global__ __launch_bounds__(NT, 1) void gemm8_kernel(GemmArgs a, HeadFuse hf) {
 }
 
 // Persistent phase-interleaved hidden layer (gemm8p_kernel; bf16, K >= 128: the default of the
-// transposed-store path and of the fused output layer; flag bit 12 selects gemm8_kernel / the
+// transposed-store path and of the fused output layer; GF_NO_P8 selects gemm8_kernel / the
 // 2-buffer loop).
 // gemm8_kernel runs ONE 256 x 256 tile per workgroup; at one workgroup per CU the matrix cores
 // idle while a fresh workgroup fills its first slices and while the last one drains its
@@ -1105,7 +1118,7 @@ __global__ __launch_bounds__(NT, 1) void gemm8_kernel(GemmArgs a, HeadFuse hf) {
 // [x T / 8, (x + 1) T / 8) and its G / 8 workgroups take every (G / 8)-th of them, so the column
 // tiles of a row block run together on one XCD and its A rows come from HBM once.
 // Measured (profiles/r5n, r5t; 1M rows, one process, interleaved): 1024 x 1024 2.04 vs 2.23 ms for
-// gemm8_kernel<false, true> (without any stores, bit 13, timing only: 1.63 ms); K = 4096 6.92 vs
+// gemm8_kernel<false, true> (without any stores, GF_P8_NOSTORE: 1.63 ms); K = 4096 6.92 vs
 // 7.42 ms; K = 256 0.25 / 0.47 vs 0.32 / 0.60 ms for the 2-buffer loop (256 / 512 units). (With the
 // builtin LDS-DMA the K = 4096 layer was slower persistent, profiles/r5m: 7.71 vs 7.37 ms.)
 // Measured and dropped (profiles/r5m, r5n): staging the next tile's A1 before the
@@ -1117,9 +1130,9 @@ constexpr int P8_MAX_MP = (160 * 1024 - 8 * HALF_B - P8_SCR) / 4;
 constexpr int P8_HEAD_MAX_OUT = P8_SCR / (4 * BM * 4);  // head partials [4 column waves][BM][n_out] fp32
 constexpr int P8_HEAD_MAX_MP = (160 * 1024 - 8 * HALF_B - P8_SCR) / (4 + 2 * P8_HEAD_MAX_OUT);  // biases + whl
 
-// NOSTORE (flag bit 13, timing only): the hidden epilogue writes nothing — the cost of the stores.
+// NOSTORE (GF_P8_NOSTORE, timing only): the hidden epilogue writes nothing — the cost of the stores.
 // (Non-temporal stores, which take 10 % off gemm_k64p_kernel, measured no change here: profiles/r5p.)
-// DEFER (flag bit 15, measured slower, profiles/r5r: 2.17-2.22 vs 2.10-2.14 ms): a tile is stored
+// DEFER (GF_P8_DEFER, measured slower, profiles/r5r: 2.17-2.22 vs 2.10-2.14 ms): a tile is stored
 // in two halves. Accumulator rows 0-1 are read by the next tile's P1 / P2, rows 2-3 only from its
 // P3 on — so rows 0-1 leave at the tile boundary and rows 2-3 after the next tile's P2, half of the
 // stores overlapping two phases of MFMAs. P4 of a tile's first slice then retires slice g + 1 with
@@ -1385,62 +1398,46 @@ int cu_count() {
   return n_cu;
 }
 
-int launch_k64p(hipStream_t stream, const GemmArgs& a) {
-  const int n_cu = cu_count();
-  const int n_ct = a.Mp / 256;
-  const int rg = std::max(1, (2 * n_cu / 8) / n_ct);  // row groups per XCD: ~2 workgroups per CU
-  // 128-byte row-segment stores through a 2 KiB wave scratch (store_hidden_seg, default: 0.565 ->
-  // 0.438 ms for 1M rows x 1024 units, TA busy 78 -> 52 %, profiles/r5f); bit 10: store_hidden_t
-  const bool seg = !((a.f32 >> 10) & 1);
-  const size_t lds = (size_t)(256 + 2 * K64_BM) * SLICE_B + 256 * 4 + (seg ? 4 * 2048 : 0);
-  // non-temporal row-segment stores (the layer streams 2 GB of output per 1M rows and reads
-  // little): 0.435 -> 0.391 ms, profiles/r5p; bit 14: ordinary stores
-  const bool nts = seg && !((a.f32 >> 14) & 1);
-  const void* kp = nts ? reinterpret_cast<const void*>(&gemm_k64p_kernel<true, true>)
-                 : seg ? reinterpret_cast<const void*>(&gemm_k64p_kernel<true>)
-                       : reinterpret_cast<const void*>(&gemm_k64p_kernel<false>);
-  if (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -5;
-  if (nts)
-    hipLaunchKernelGGL((gemm_k64p_kernel<true, true>), dim3(8 * n_ct * rg), dim3(K64_NT), lds, stream, a, rg);
-  else if (seg)
-    hipLaunchKernelGGL(gemm_k64p_kernel<true>, dim3(8 * n_ct * rg), dim3(K64_NT), lds, stream, a, rg);
-  else
-    hipLaunchKernelGGL(gemm_k64p_kernel<false>, dim3(8 * n_ct * rg), dim3(K64_NT), lds, stream, a, rg);
+// Raise the kernel's dynamic-LDS limit to `lds` (on every launch), then launch it.
+template <typename... P, typename... Args>
+int launch_dyn(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -5;
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
   return 0;
+}
+
+// One K = 64 tile per workgroup: 48 KiB of LDS, no attribute to raise.
+template <bool PREP, bool TST>
+int launch_k64(hipStream_t stream, const GemmArgs& a, const PrepArgs& p) {
+  const size_t lds = (size_t)(K64_BM + 256) * SLICE_B;
+  hipLaunchKernelGGL((gemm_k64_kernel<PREP, TST>), dim3((a.rows_p / K64_BM) * (a.Mp / 256)), dim3(K64_NT), lds, stream, a, p);
+  return 0;
+}
+
+// SEG: 128-byte row-segment stores through a 2 KiB wave scratch (store_hidden_seg, default: 0.565 ->
+// 0.438 ms for 1M rows x 1024 units, TA busy 78 -> 52 %, profiles/r5g); GF_K64P_T: store_hidden_t.
+// NTS: non-temporal row-segment stores (the layer streams 2 GB of output per 1M rows and reads
+// little): 0.435 -> 0.391 ms, profiles/r5q; GF_K64P_TEMPORAL: ordinary stores.
+template <bool SEG, bool NTS = false>
+int launch_k64p(hipStream_t stream, const GemmArgs& a) {
+  const int n_ct = a.Mp / 256;
+  const int rg = std::max(1, (2 * cu_count() / 8) / n_ct);  // row groups per XCD: ~2 workgroups per CU
+  const size_t lds = (size_t)(256 + 2 * K64_BM) * SLICE_B + 256 * 4 + (SEG ? 4 * 2048 : 0);
+  return launch_dyn(gemm_k64p_kernel<SEG, NTS>, dim3(8 * n_ct * rg), dim3(K64_NT), lds, stream, a, rg);
 }
 
 template <bool HEADF, bool TST = false>
-int launch8(hipStream_t stream, const GemmArgs& a, const HeadFuse& hf) {
+int launch8(hipStream_t stream, const GemmArgs& a, const HeadFuse& hf = {}) {
   const size_t lds = 8 * (size_t)HALF_B;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8_kernel<HEADF, TST>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return -5;
-  hipLaunchKernelGGL((gemm8_kernel<HEADF, TST>), dim3((a.rows_p / BM) * (a.Mp / 256)), dim3(NT), lds, stream, a, hf);
-  return 0;
+  return launch_dyn(gemm8_kernel<HEADF, TST>, dim3((a.rows_p / BM) * (a.Mp / 256)), dim3(NT), lds, stream, a, hf);
 }
 
-template <bool HEADF>
-int launch8p(hipStream_t stream, const GemmArgs& a, const HeadFuse& hf) {
+template <bool HEADF, bool NOSTORE = false, bool DEFER = false>
+int launch8p(hipStream_t stream, const GemmArgs& a, const HeadFuse& hf = {}) {
   const size_t lds = 8 * (size_t)HALF_B + P8_SCR + 4 * (size_t)a.Mp + (HEADF ? 2 * (size_t)hf.n_out * a.Mp : 0);
-  const bool nostore = !HEADF && ((a.f32 >> 13) & 1), defer = !HEADF && !nostore && ((a.f32 >> 15) & 1);
-  const void* kp = HEADF ? reinterpret_cast<const void*>(&gemm8p_kernel<true, false>)
-                 : nostore ? reinterpret_cast<const void*>(&gemm8p_kernel<false, true>)
-                 : defer ? reinterpret_cast<const void*>(&gemm8p_kernel<false, false, true>)
-                         : reinterpret_cast<const void*>(&gemm8p_kernel<false, false>);
-  if (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -5;
   const int total = (a.rows_p / BM) * (a.Mp / 256);
-  const int grid = std::min(total, cu_count());
-  if (HEADF) hipLaunchKernelGGL((gemm8p_kernel<true, false>), dim3(grid), dim3(NT), lds, stream, a, hf);
-  else if (nostore) hipLaunchKernelGGL((gemm8p_kernel<false, true>), dim3(grid), dim3(NT), lds, stream, a, hf);
-  else if (defer) hipLaunchKernelGGL((gemm8p_kernel<false, false, true>), dim3(grid), dim3(NT), lds, stream, a, hf);
-  else hipLaunchKernelGGL((gemm8p_kernel<false, false>), dim3(grid), dim3(NT), lds, stream, a, hf);
-  return 0;
-}
-
-// whether the persistent kernel takes a layer (a: the hidden layer's args; flag bit 12 opts out)
-bool use8p(const GemmArgs& a) {
-  return !((a.f32 >> 12) & 1) && a.Mp <= P8_MAX_MP && (size_t)a.lda * 2 * BM < (1ull << 31) &&
-         (size_t)a.ldw * 2 * 256 < (1ull << 31);
+  return launch_dyn(gemm8p_kernel<HEADF, NOSTORE, DEFER>, dim3(std::min(total, cu_count())), dim3(NT), lds, stream, a, hf);
 }
 
 // The fused output layer's second half: one thread per row sums the column tiles' partials in
@@ -1462,12 +1459,82 @@ int launch(hipStream_t stream, const GemmArgs& a) {
   const size_t stage = 2 * (size_t)BM * SLICE_B + 2 * (size_t)BN * SLICE_B;
   const size_t head = HEAD ? (size_t)BM * HEAD_LD * 4 : 0;
   const size_t lds = stage > head ? stage : head;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BN, HEAD, F32, TST>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return -5;
-  dim3 grid((a.rows_p / BM) * (a.Mp / BN));
-  hipLaunchKernelGGL((gemm_kernel<BN, HEAD, F32, TST>), grid, dim3(NT), lds, stream, a);
-  return 0;
+  return launch_dyn(gemm_kernel<BN, HEAD, F32, TST>, dim3((a.rows_p / BM) * (a.Mp / BN)), dim3(NT), lds, stream, a);
+}
+
+// Every instantiation a layer can be routed to, from 1 in this order (what pmml_gemm_route returns;
+// tests/test_gpu_gemm_route.py holds the names in the same order).
+enum GemmKernel {
+  GK_NONE = 0,  // nothing to launch (rows <= 0)
+  // gemm_kernel<32, true, true>, <256, false, true>, <32, true, false>, <256, false, false, true>, <256, false, false>
+  GK_GEMM_HEAD_F32, GK_GEMM_F32, GK_GEMM_HEAD, GK_GEMM_T, GK_GEMM,
+  GK_K64_T, GK_K64,                                   // gemm_k64_kernel<false, true>, <false, false>
+  GK_K64P_NTS, GK_K64P_SEG, GK_K64P_T,                // gemm_k64p_kernel<true, true>, <true>, <false>
+  GK_G8_T, GK_G8, GK_G8_HEAD,                         // gemm8_kernel<false, true>, <false, false>, <true, false>
+  GK_G8P, GK_G8P_NOSTORE, GK_G8P_DEFER, GK_G8P_HEAD,  // gemm8p_kernel<false, false>, <false, true>, <false, false, true>, <true, false>
+};
+
+bool misaligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) & 15; }
+
+// A and Wt of a layer: sk the K slice of the operand type, bn the unit tile
+bool operands_bad(const GemmArgs& a, int sk, int bn) {
+  return a.rows_p % BM || a.rows_p < a.rows || a.K % sk || a.K <= 0 || a.Mp % bn || a.Mp <= 0 || (a.lda & 7) ||
+         (a.ldw & 7) || a.lda < a.K || a.ldw < a.K || misaligned16(a.A) || misaligned16(a.Wt);
+}
+
+bool hidden_out_bad(const GemmArgs& a) { return (a.ldc & 7) || a.ldc < a.Mp || !a.C || misaligned16(a.C); }
+
+// gemm8p_kernel's limits: every unit's bias in LDS, 32-bit byte offsets inside a row / column tile
+bool p8_fits(const GemmArgs& a) {
+  return a.Mp <= P8_MAX_MP && (size_t)a.lda * 2 * BM < (1ull << 31) && (size_t)a.ldw * 2 * 256 < (1ull << 31);
+}
+
+// Which kernel pmml_gemm_launch runs: 0 for no rows, -4 for args it refuses, else a GemmKernel.
+// head = 0: hidden layer (BN 256, output C in the operand type); head = 1: output layer (BN 32,
+// n_out <= 32, decode). Makes no HIP call and follows no pointer.
+int route(const GemmArgs& a, int head) {
+  if (a.rows <= 0) return GK_NONE;
+  if (a.flags & ~GF_ALL) return -4;
+  const bool f32 = a.flags & GF_F32;
+  if (operands_bad(a, f32 ? SLICE_B / 4 : SLICE_B / 2, head ? 32 : 256)) return -4;
+  if (head) {
+    if (a.n_out < 1 || a.n_out > 32 || a.Mp != 32 || (!a.C && (!a.row_ok || !a.score || !a.valid))) return -4;
+    if (a.C && (a.ldc < a.n_out || (reinterpret_cast<uintptr_t>(a.C) & 3))) return -4;
+    return f32 ? GK_GEMM_HEAD_F32 : GK_GEMM_HEAD;
+  }
+  if (hidden_out_bad(a)) return -4;
+  if (f32) return GK_GEMM_F32;
+  // transposed-accumulator stores (store_hidden_t) unless the direct stores or their LDS epilogue are asked for
+  const bool tst = !(a.flags & (GF_DIRECT | GF_WAVE_EPI));
+  if (a.K == 64 && !(a.flags & GF_K64_WIDE)) {  // the 128-row K = 64 kernels; persistent on the transposed-store path
+    if (!tst) return GK_K64;
+    if (a.flags & GF_K64_TILE) return GK_K64_T;
+    return a.flags & GF_K64P_T ? GK_K64P_T : a.flags & GF_K64P_TEMPORAL ? GK_K64P_SEG : GK_K64P_NTS;
+  }
+  // K >= 128 (GF_PH8: also K = 64 on the 256 x 256 tile) on the transposed-store path with the
+  // row-segment stores: the persistent kernel, where it fits (profiles/r5u: K = 256 layers 0.25 /
+  // 0.47 vs 0.32 / 0.60 ms on the 2-buffer loop, K = 4096 6.92 vs 7.42 ms on gemm8_kernel).
+  // GF_P8_NOSTORE and GF_P8_ANY take it past p8_fits and past GF_NO_P8.
+  const bool ph8 = a.flags & GF_PH8;
+  if (tst && !(a.flags & GF_PH8_T) && (a.K >= 128 || ph8) &&
+      ((!(a.flags & GF_NO_P8) && p8_fits(a)) || (a.flags & (GF_P8_NOSTORE | GF_P8_ANY))))
+    return a.flags & GF_P8_NOSTORE ? GK_G8P_NOSTORE : a.flags & GF_P8_DEFER ? GK_G8P_DEFER : GK_G8P;
+  // else one tile per workgroup: phase-interleaved from K = 512 (profiles/r3ao: 2048 x 2048 8.73 ->
+  // 8.36 ms, 1024 x 1024 2.62 -> 2.48 ms over 1M rows); below that the layer is bound by its output
+  // writes and the 2-buffer loop is faster (K = 64: 0.83 vs 0.92 ms)
+  if (ph8 || a.K >= 512) return tst ? GK_G8_T : GK_G8;
+  return tst ? GK_GEMM_T : GK_GEMM;
+}
+
+// The same for pmml_gemm_fused_head_launch (a: the last hidden layer, o: the output layer): bf16
+// only, so GF_PH8 is moot; of the flags only GF_NO_P8 is read.
+int route_fused_head(const GemmArgs& a, const GemmArgs& o) {
+  if (a.rows <= 0) return GK_NONE;
+  if ((a.flags | o.flags) & GF_F32) return -4;
+  if (operands_bad(a, BK, 256)) return -4;
+  if (o.n_out < 1 || o.n_out > 32 || o.K != a.Mp || o.rows != a.rows || o.rows_p != a.rows_p) return -4;
+  if (!o.row_ok || !o.score || !o.valid) return -4;
+  return !(a.flags & GF_NO_P8) && p8_fits(a) && o.n_out <= P8_HEAD_MAX_OUT && a.Mp <= P8_HEAD_MAX_MP ? GK_G8P_HEAD : GK_G8_HEAD;
 }
 
 }  // namespace
@@ -1478,11 +1545,10 @@ PMML_API int pmml_nn_prep_args_size() { return (int)sizeof(PrepArgs); }
 PMML_API int pmml_nn_prep_launch(hipStream_t stream, const PrepArgs* args) {
   PrepArgs a = *args;
   if (a.rows_p <= 0) return 0;
-  if ((a.k0 & 7) || a.k0 < a.n_in || a.k0 > NN_MAX_INPUTS || (a.ldh & 7) || (reinterpret_cast<uintptr_t>(a.H) & 15))
-    return -4;
+  if ((a.k0 & 7) || a.k0 < a.n_in || a.k0 > NN_MAX_INPUTS || (a.ldh & 7) || misaligned16(a.H)) return -4;
   if (a.f32 != 0 && a.f32 != 1) return -4;
   // the vector path needs every row's first input 16-byte aligned
-  if (a.contig && ((reinterpret_cast<uintptr_t>(a.X) & 15) || (a.ldx & 3))) a.contig = 0;
+  if (a.contig && (misaligned16(a.X) || (a.ldx & 3))) a.contig = 0;
   int g = 0;
   while ((1 << g) < (a.k0 >> 3) && g < 6) ++g;  // lanes per row: chunks rounded up to a power of two, <= 64
   const long long threads = (long long)a.rows_p << g;
@@ -1492,52 +1558,29 @@ PMML_API int pmml_nn_prep_launch(hipStream_t stream, const PrepArgs* args) {
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 
-// head = 0: hidden layer (BN 256, output C in the operand type); head = 1: output layer (BN 32,
-// n_out <= 32, decode). args->f32 selects bf16 (0) or fp32 (1) operands.
+// One layer on the kernel route() names (args->flags: bf16 or fp32 operands, experiment bits).
 PMML_API int pmml_gemm_launch(hipStream_t stream, const GemmArgs* args, int head) {
   const GemmArgs a = *args;
-  if (a.rows <= 0) return 0;
-  const int BN = head ? 32 : 256;
-  if (a.f32 & ~0x1FFE1) return -4;
-  // bf16 hidden layers with K >= 512 run the phase-interleaved kernel (profiles/r3ao: 2048 x 2048
-  // 8.73 -> 8.36 ms, 1024 x 1024 2.62 -> 2.48 ms over 1M rows); below that the layer is bound by
-  // its output writes and the 2-buffer loop is faster (K = 64: 0.83 vs 0.92 ms). Bit 7 forces it.
-  const int f32 = a.f32 & 1, ph8 = !f32 && (((a.f32 >> 7) & 1) || a.K >= 512);
-  const int sk = f32 ? SLICE_B / 4 : SLICE_B / 2;
-  if (a.rows_p % BM || a.rows_p < a.rows || a.K % sk || a.K <= 0 || a.Mp % BN || a.Mp <= 0) return -4;
-  if ((a.lda & 7) || (a.ldw & 7) || a.lda < a.K || a.ldw < a.K) return -4;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.Wt) & 15)) return -4;
-  if (head && (a.n_out < 1 || a.n_out > 32 || a.Mp != 32 || (!a.C && (!a.row_ok || !a.score || !a.valid)))) return -4;
-  if (head && a.C && (a.ldc < a.n_out || (reinterpret_cast<uintptr_t>(a.C) & 3))) return -4;
-  if (!head && ((a.ldc & 7) || a.ldc < a.Mp || !a.C || (reinterpret_cast<uintptr_t>(a.C) & 15))) return -4;
-  // transposed-accumulator stores (store_hidden_t) unless bit 8 or the bit-5 LDS epilogue asks otherwise
-  const bool tst = !((a.f32 >> 8) & 1) && !((a.f32 >> 5) & 1);
-  if (!head && !f32 && a.K == 64 && !((a.f32 >> 6) & 1)) {  // bit 6 forces the 256 x 256 tile
-    const dim3 grid((a.rows_p / K64_BM) * (a.Mp / 256));
-    const size_t lds = (size_t)(K64_BM + 256) * SLICE_B;
-    if (tst && !((a.f32 >> 9) & 1)) {  // bit 9: the one-tile-per-workgroup kernel
-      const int rc = launch_k64p(stream, a);
-      if (rc) return rc;
-    } else if (tst) {
-      hipLaunchKernelGGL((gemm_k64_kernel<false, true>), grid, dim3(K64_NT), lds, stream, a, PrepArgs{});
-    } else {
-      hipLaunchKernelGGL((gemm_k64_kernel<false, false>), grid, dim3(K64_NT), lds, stream, a, PrepArgs{});
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+  const int k = route(a, head);
+  if (k <= 0) return k;
+  int rc = -4;
+  switch (k) {
+    case GK_GEMM_HEAD_F32: rc = launch<32, true, true>(stream, a); break;
+    case GK_GEMM_F32: rc = launch<256, false, true>(stream, a); break;
+    case GK_GEMM_HEAD: rc = launch<32, true, false>(stream, a); break;
+    case GK_GEMM_T: rc = launch<256, false, false, true>(stream, a); break;
+    case GK_GEMM: rc = launch<256, false, false>(stream, a); break;
+    case GK_K64_T: rc = launch_k64<false, true>(stream, a, PrepArgs{}); break;
+    case GK_K64: rc = launch_k64<false, false>(stream, a, PrepArgs{}); break;
+    case GK_K64P_NTS: rc = launch_k64p<true, true>(stream, a); break;
+    case GK_K64P_SEG: rc = launch_k64p<true>(stream, a); break;
+    case GK_K64P_T: rc = launch_k64p<false>(stream, a); break;
+    case GK_G8_T: rc = launch8<false, true>(stream, a); break;
+    case GK_G8: rc = launch8<false, false>(stream, a); break;
+    case GK_G8P: rc = launch8p<false>(stream, a); break;
+    case GK_G8P_NOSTORE: rc = launch8p<false, true>(stream, a); break;
+    case GK_G8P_DEFER: rc = launch8p<false, false, true>(stream, a); break;
   }
-  // persistent tile walk (gemm8p_kernel) for the transposed-store phase-interleaved layers with the
-  // row-segment stores and K <= 1024, unless bit 12 (one tile per workgroup) or bit 11
-  // (store_hidden_t) is set
-  // bf16 hidden layers with K >= 128 (bit 7: also K = 64) on the transposed-store path run the
-  // persistent kernel (profiles/r5t: K = 256 layers 0.25 / 0.47 vs 0.32 / 0.60 ms on the 2-buffer
-  // loop, K = 4096 6.92 vs 7.42 ms on gemm8_kernel)
-  const bool p8 = !f32 && tst && !head && !((a.f32 >> 11) & 1) && (a.K >= 128 || ((a.f32 >> 7) & 1)) &&
-                  (use8p(a) || ((a.f32 >> 13) & 1) || ((a.f32 >> 16) & 1));
-  const int rc = f32 ? (head ? launch<32, true, true>(stream, a) : launch<256, false, true>(stream, a))
-                     : (head ? launch<32, true, false>(stream, a)
-                             : (p8 ? launch8p<false>(stream, a, HeadFuse{})
-                                   : ph8 ? (tst ? launch8<false, true>(stream, a, HeadFuse{}) : launch8<false, false>(stream, a, HeadFuse{}))
-                                   : (tst ? launch<256, false, false, true>(stream, a) : launch<256, false, false>(stream, a))));
   if (rc) return rc;
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
@@ -1550,20 +1593,20 @@ PMML_API int pmml_gemm_fused_head_launch(hipStream_t stream, const GemmArgs* hid
                                          const void* wh_perm, float* part) {
   const GemmArgs a = *hidden;
   const GemmArgs o = *head;
-  if (a.rows <= 0) return 0;
-  if ((a.f32 & 1) || (o.f32 & 1)) return -4;  // bf16 only (bit 7, the gemm8 force flag, is moot here)
-  if (a.rows_p % BM || a.rows_p < a.rows || a.K % BK || a.K <= 0 || a.Mp % 256 || a.Mp <= 0) return -4;
-  if ((a.lda & 7) || (a.ldw & 7) || a.lda < a.K || a.ldw < a.K) return -4;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.Wt) & 15)) return -4;
-  if (o.n_out < 1 || o.n_out > 32 || o.K != a.Mp || o.rows != a.rows || o.rows_p != a.rows_p) return -4;
-  if (!o.row_ok || !o.score || !o.valid || !part || !wh_perm || (reinterpret_cast<uintptr_t>(wh_perm) & 15)) return -4;
+  const int k = route_fused_head(a, o);
+  if (k <= 0) return k;
+  if (!part || !wh_perm || misaligned16(wh_perm)) return -4;
   HeadFuse hf{static_cast<const __bf16*>(wh_perm), part, a.Mp, o.n_out};
-  const bool p8 = use8p(a) && o.n_out <= P8_HEAD_MAX_OUT && a.Mp <= P8_HEAD_MAX_MP;
-  int rc = p8 ? launch8p<true>(stream, a, hf) : launch8<true, false>(stream, a, hf);
+  int rc = k == GK_G8P_HEAD ? launch8p<true>(stream, a, hf) : launch8<true, false>(stream, a, hf);
   if (rc) return rc;
   hipLaunchKernelGGL(nn_head_decode_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, stream, o, part, a.Mp / 256);
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
+
+// What the two entries above would launch for these args (a GemmKernel id, 0 or -4), for tests:
+// they launch nothing and never dereference a pointer in the args.
+PMML_API int pmml_gemm_route(const GemmArgs* args, int head) { return route(*args, head); }
+PMML_API int pmml_gemm_fused_head_route(const GemmArgs* a, const GemmArgs* o) { return route_fused_head(*a, *o); }
 
 // Input stage + first hidden layer in one launch (gemm_k64_kernel<true>): bf16, K = k0 = 64 (at
 // most 64 network inputs), hidden-layer output C; p->row_ok receives the row validity as
@@ -1572,16 +1615,12 @@ PMML_API int pmml_nn_first_layer_launch(hipStream_t stream, const GemmArgs* args
   const GemmArgs a = *args;
   const PrepArgs p = *prep;
   if (a.rows <= 0) return 0;
-  if ((a.f32 & 1) || p.f32 != 0 || a.K != 64 || p.k0 != 64 || p.n_in > 64 || p.n_in < 0) return -4;
+  if ((a.flags & GF_F32) || p.f32 != 0 || a.K != 64 || p.k0 != 64 || p.n_in > 64 || p.n_in < 0) return -4;
   if (a.rows_p % 256 || a.rows_p < a.rows || p.rows_p != a.rows_p || p.n_rows != a.rows) return -4;
-  if (a.Mp % 256 || a.Mp <= 0 || (a.ldw & 7) || a.ldw < a.K || (reinterpret_cast<uintptr_t>(a.Wt) & 15)) return -4;
-  if ((a.ldc & 7) || a.ldc < a.Mp || !a.C || (reinterpret_cast<uintptr_t>(a.C) & 15) || !p.row_ok || !p.X) return -4;
-  const dim3 grid((a.rows_p / K64_BM) * (a.Mp / 256));
-  const size_t lds = (size_t)(K64_BM + 256) * SLICE_B;
-  if (!((a.f32 >> 8) & 1) && !((a.f32 >> 5) & 1))
-    hipLaunchKernelGGL((gemm_k64_kernel<true, true>), grid, dim3(K64_NT), lds, stream, a, p);
-  else
-    hipLaunchKernelGGL((gemm_k64_kernel<true, false>), grid, dim3(K64_NT), lds, stream, a, p);
+  if (a.Mp % 256 || a.Mp <= 0 || (a.ldw & 7) || a.ldw < a.K || misaligned16(a.Wt)) return -4;
+  if (hidden_out_bad(a) || !p.row_ok || !p.X) return -4;
+  if (!(a.flags & (GF_DIRECT | GF_WAVE_EPI))) launch_k64<true, true>(stream, a, p);
+  else launch_k64<true, false>(stream, a, p);
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

@@ -420,7 +420,7 @@ class WideMlpPlan(MlpPlan):
         self.bss = self._t(np.concatenate(bss))
         self.dims = dims
 
-    gemm_flags = 0  # experiment bits ORed into GemmArgs.f32 (scripts/gemm_ab.py); the kernel rejects unknown bits
+    gemm_flags = 0  # experiment bits ORed into GemmArgs.flags: enum GemmFlag in csrc/gemm.hip (unknown bits are rejected)
     # bf16: the last hidden layer and the output layer in one GEMM launch (gemm8_kernel<true>) — the
     # last hidden activations never reach HBM (profiles/r4f)
     fuse_head = True
@@ -494,7 +494,7 @@ class WideMlpPlan(MlpPlan):
         for li, (kp, mp, act, thr, wo, bo) in enumerate(self.dims):
             head = li == len(self.dims) - 1
             a = GemmArgs()
-            a.A, a.Wt, a.bias, a.f32 = cur.data_ptr(), wbase + es * wo, bbase + 4 * bo, (1 - self.bf16) | self.gemm_flags
+            a.A, a.Wt, a.bias, a.flags = cur.data_ptr(), wbase + es * wo, bbase + 4 * bo, (1 - self.bf16) | self.gemm_flags
             a.rows, a.rows_p, a.K, a.Mp = n, rows_p, kp, mp
             a.lda, a.ldw, a.act, a.thr = lda, kp, act, thr
             if li == 0 and first:  # input stage + first hidden layer: one launch, no [rows, 64] round trip

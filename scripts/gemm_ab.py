@@ -3,10 +3,10 @@
 device time per launch over 1M device-resident rows; also checks that every variant produces the
 same scores as the first. Prints one JSON line per variant.
 
-A variant is a value of ``GemmArgs.f32``'s experiment bits, set through ``plan.gemm_flags`` (the
-plan ORs it into the launch). The round-3 experiments (``profiles/r3ak/``: bit 4 = LDS swizzle,
-bit 5 = 4-wave pipelined loop) were measured and folded in or removed; with no experiment bits
-compiled in, run it with ``VARIANTS=0`` to time the shipped kernel."""
+A variant is a value of the experiment bits of ``GemmArgs.flags``, set through ``plan.gemm_flags``
+(the plan ORs it into every layer's launch). ``enum GemmFlag`` in ``ops/csrc/gemm.hip`` names the
+bits (5 to 16) and what each selects; a value with any other bit set is refused. ``VARIANTS=0``
+times the shipped routing alone, ``VARIANTS=0,0x1000`` compares it with one tile per workgroup."""
 import json
 import os
 import sys
