@@ -18,7 +18,7 @@ benchmark measures the real load → compile → score path.
 from __future__ import annotations
 
 import io
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -540,6 +540,64 @@ def scorecard_pmml(n_features: int = 4, seed: int = 0, reason_codes: bool = True
               'operator="equal" value="blue"/></Attribute>\n')
     out.write(f'    <Attribute partialScore="{rng.uniform(0, 20):.3f}"><True/></Attribute>\n')
     out.write('   </Characteristic>\n  </Characteristics>\n </Scorecard>\n</PMML>\n')
+    return out.getvalue()
+
+
+def reason_scorecard_pmml(characteristics: Sequence[dict], n_features: int, ranks: Sequence[int] = (1, 2),
+                          algorithm: str = "pointsBelow", baseline: Optional[float] = None,
+                          use_reason_codes: bool = True, initial_score: float = 0.0,
+                          intervals: Optional[dict] = None, mining: Optional[dict] = None) -> str:
+    """``Scorecard`` over the continuous fields ``f0 .. f{n_features - 1}`` whose characteristics,
+    partial scores, reason codes and baselines the caller chooses.
+
+    ``characteristics``: dicts ``{"name", "reason_code", "baseline", "attributes"}``; an attribute is
+    a dict ``{"predicate": XML text, "partial": float, "reason_code", "complex": expression XML}``
+    (every key but ``predicate`` optional; ``complex`` becomes a ``ComplexPartialScore``). Numbers are
+    written with ``repr``, so a float64 reads back exactly. ``ranks``: one ``reasonCode`` Output
+    field ``RC<rank>`` per entry. ``intervals``: ``{field index: (lo, hi)}`` closed validity
+    intervals (a value outside fails the row); ``mining``: ``{field index: extra MiningField
+    attributes}``."""
+    out = io.StringIO()
+    _header(out, "synthetic scorecard with chosen reason codes")
+    out.write(f' <DataDictionary numberOfFields="{n_features + 1}">\n')
+    for j in range(n_features):
+        iv = (intervals or {}).get(j)
+        body = "" if iv is None else (f'<Interval closure="closedClosed" leftMargin="{float(iv[0])!r}" '
+                                      f'rightMargin="{float(iv[1])!r}"/>')
+        out.write(f'  <DataField name="f{j}" optype="continuous" dataType="double">{body}</DataField>\n')
+    out.write('  <DataField name="score" optype="continuous" dataType="double"/>\n </DataDictionary>\n')
+    attrs = f' useReasonCodes="{"true" if use_reason_codes else "false"}" reasonCodeAlgorithm="{algorithm}"'
+    if baseline is not None:
+        attrs += f' baselineScore="{float(baseline)!r}"'
+    out.write(f' <Scorecard functionName="regression" initialScore="{float(initial_score)!r}"{attrs}>\n')
+    out.write('  <MiningSchema>\n   <MiningField name="score" usageType="target"/>\n')
+    for j in range(n_features):
+        extra = (mining or {}).get(j, "")
+        out.write(f'   <MiningField name="f{j}"{" " + extra if extra else ""}/>\n')
+    out.write('  </MiningSchema>\n')
+    if ranks:
+        out.write('  <Output>\n')
+        for r in ranks:
+            out.write(f'   <OutputField name="RC{int(r)}" feature="reasonCode" rank="{int(r)}" dataType="string"/>\n')
+        out.write('  </Output>\n')
+    out.write('  <Characteristics>\n')
+    for i, ch in enumerate(characteristics):
+        head = f'   <Characteristic name="{ch.get("name") or f"ch{i}"}"'
+        if ch.get("reason_code") is not None:
+            head += f' reasonCode="{ch["reason_code"]}"'
+        if ch.get("baseline") is not None:
+            head += f' baselineScore="{float(ch["baseline"])!r}"'
+        out.write(head + '>\n')
+        for a in ch["attributes"]:
+            tag = '    <Attribute'
+            if a.get("partial") is not None:
+                tag += f' partialScore="{float(a["partial"])!r}"'
+            if a.get("reason_code") is not None:
+                tag += f' reasonCode="{a["reason_code"]}"'
+            cps = f'<ComplexPartialScore>{a["complex"]}</ComplexPartialScore>' if a.get("complex") else ""
+            out.write(f'{tag}>{a["predicate"]}{cps}</Attribute>\n')
+        out.write('   </Characteristic>\n')
+    out.write('  </Characteristics>\n </Scorecard>\n</PMML>\n')
     return out.getvalue()
 
 

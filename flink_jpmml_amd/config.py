@@ -54,6 +54,11 @@ class ScoringConfig:
     oracle (batched, vectorised) and count ``scoring.host_fallback``; ``warn`` — the same plus one
     WARNING per model; ``error`` — fail the model load (strict production setting)."""
 
+    reason_codes: bool = False
+    """Rank a Scorecard's ``reasonCode`` Output fields (rank 1 … 8) on the device when a batch is
+    scored with ``outputs=True`` (``FJA_REASON_CODES=1``). Off: such a field does not lower, and the
+    Output fields of that model follow ``fallback``. Other models ignore it."""
+
     host_threads: int = 0
     """Worker threads of the native host tree walk (``fallback="host"`` models, CPU-only ranks,
     direct CPU ``predict_batch``); 0 = ``FJA_HOST_THREADS`` or 1. Results do not depend on it."""
@@ -153,7 +158,8 @@ class ScoringConfig:
                   micro_batch=get("MICRO_BATCH", int), cache_capacity=get("CACHE_CAPACITY", int),
                   checkpoint_dir=get("CHECKPOINT_DIR", str), watchdog_s=get("WATCHDOG_S", float),
                   graph_max_rows=get("GRAPH_MAX_ROWS", int), metrics_port=get("METRICS_PORT", int),
-                  host_threads=get("HOST_THREADS", int))
+                  host_threads=get("HOST_THREADS", int),
+                  reason_codes=get("REASON_CODES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")))
         kw = {k: v for k, v in kw.items() if v is not None}
         kw.update({k: v for k, v in overrides.items() if v is not None})
         return ScoringConfig(**kw)

@@ -17,7 +17,12 @@ kernels are the existing ones:
   column and the GENERAL tree kernel adds it (``tree.hip`` ``vcol``); a missing expression value
   voids the score. :class:`ComplexScorecardEvaluator` is the direct formulation kept for the
   tests. Reason codes
-  (``useReasonCodes``, ``pointsBelow`` / ``pointsAbove``) are host outputs.
+  (``useReasonCodes``, ``pointsBelow`` / ``pointsAbove``): :class:`_ReasonCodes` is the host
+  oracle (a dict per row, stably sorted by descending summed difference). An output plan asked with
+  ``reason_codes=True`` ranks them on the device instead (``runtime/reasons.py`` lowers the
+  characteristics, ``ops/csrc/reasons.hip`` picks, sums in float64 and ranks with the oracle's tie
+  rule: the code touched first on the row); without the switch a ``reasonCode`` Output field does
+  not lower and follows the fallback policy.
 * **RuleSetModel** ``firstHit`` = a one-level ``TreeModel``: the (flattened) rules are the root's
   children in document order, a ``CompoundRule``'s predicate AND-ed into its rules; the
   ``defaultScore`` sits on the root (``returnLastPrediction``). ``weightedMax`` is ``firstHit`` over

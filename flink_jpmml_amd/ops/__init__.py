@@ -4,7 +4,9 @@ Kernels (``csrc/``): ``tree.hip`` (perfect / pointer / wide tree-ensemble traver
 reduce), ``cluster.hip`` (center-based clustering), ``linear.hip`` (regression tables + links),
 ``mlp.hip`` (fused all-layer MFMA MLP, bf16 and fp32), ``svm.hip`` (kernel eval + votes),
 ``sparse.hip`` (CSR record batches expanded into the dense input tile; wrapper and numpy twin in
-``sparse.py``), ``host.hip`` (zero-copy / copy helpers). Shared device code: ``common.h`` (field preparation,
+``sparse.py``), ``outputs.hip`` (Output fields and top-k classes; ``outputs.py``), ``reasons.hip``
+(ranked Scorecard reason codes; wrapper, packed tables and numpy twin in ``reasons.py``),
+``host.hip`` (zero-copy / copy helpers). Shared device code: ``common.h`` (field preparation,
 LDS staging), ``epilogue.h`` (fused target decode).
 """
 

@@ -280,7 +280,17 @@ class OutputArgs(ctypes.Structure):
                 ("n_col", c_int), ("ldo", c_int), ("k", c_int), ("n_tables", c_int), ("n_labels", c_int)]
 
 
+class ReasonArgs(ctypes.Structure):
+    """reasons.hip ReasonArgs: the packed scorecard and the scored rows -> their ranked reason codes."""
+    _fields_ = [("X", c_void_p), ("prep", c_void_p), ("valid", c_void_p), ("chars", c_void_p), ("attrs", c_void_p),
+                ("dval", c_void_p), ("preds", c_void_p), ("pool", c_void_p), ("cols", c_void_p), ("tables", c_void_p),
+                ("out", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("ldo", c_int),
+                ("n_char", c_int), ("n_code", c_int), ("n_col", c_int), ("k", c_int), ("above", c_int),
+                ("shared", c_int), ("feat_lds", c_int), ("rows", c_int), ("n_tables", c_int), ("pad", c_int)]
+
+
 _ABI = {
+    "pmml_reasons_args_size": ReasonArgs,
     "pmml_outputs_args_size": OutputArgs,
     "pmml_csr_expand_args_size": CsrExpandArgs,
     "pmml_segment_args_size": SegArgs,
@@ -427,6 +437,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_outputs_launch.restype = c_int
         lib.pmml_outputs_rows.argtypes = [c_int, c_int]
         lib.pmml_outputs_rows.restype = c_int
+        lib.pmml_reasons_launch.argtypes = [c_void_p, ctypes.POINTER(ReasonArgs)]
+        lib.pmml_reasons_launch.restype = c_int
+        lib.pmml_reasons_lds_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+        lib.pmml_reasons_lds_bytes.restype = ctypes.c_longlong
         _lib = lib
         return lib
 

@@ -119,16 +119,17 @@ class CompiledPmml:
         return s, v, cols
 
     # ------------------------------------------------------------------ device
-    def output_plan(self, device: Any = "cuda", top_k: int = 0, **opts):
+    def output_plan(self, device: Any = "cuda", top_k: int = 0, reason_codes: bool = False, **opts):
         """The :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan` of this model, lowered once per
-        (device, top_k, options) and cached like :meth:`plan`."""
+        (device, top_k, reason_codes, options) and cached like :meth:`plan`. ``reason_codes`` ranks a
+        Scorecard's ``reasonCode`` fields on the device; other models ignore it."""
         from .outputs import OutputPlan
 
-        key = f"outputs|{device}|{int(top_k)}|{sorted(opts.items())}"
+        key = f"outputs|{device}|{int(top_k)}|{bool(reason_codes)}|{sorted(opts.items())}"
         with self._lock:
             p = self._plans.get(key)
             if p is None:
-                p = OutputPlan(self, device, top_k=top_k, **opts)
+                p = OutputPlan(self, device, top_k=top_k, reason_codes=bool(reason_codes), **opts)
                 self._plans[key] = p
             return p
 

@@ -257,6 +257,7 @@ class StreamingScorer:
         self._out_lock = threading.Lock()
         self.fallback = "warn"
         self.lowering_opts: dict = {}
+        self.reason_codes = False  # ScoringConfig.reason_codes: passed to output_plan only
         self._row_state = None  # score_row's persistent buffers
         self._row_lock = threading.Lock()  # ...shared by every caller of score_row
         from ..ops import _lib
@@ -466,7 +467,8 @@ class StreamingScorer:
                 "Output fields need the PMML document: this scorer's plan arrived by replication "
                 "without it (bind the model from its document on this rank)")
         try:
-            return compiled.output_plan(self.device, top_k=top_k, **self.lowering_opts)
+            return compiled.output_plan(self.device, top_k=top_k, reason_codes=self.reason_codes,
+                                        **self.lowering_opts)
         except NotLowerable as e:
             if self.fallback == "error":
                 raise
@@ -840,6 +842,7 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
         pipeline = DevicePipeline(plan.device, cfg.micro_batch, cfg.pipeline_depth, cfg.h2d_streams)
     scorer = StreamingScorer(plan, pipeline=pipeline, max_inflight=cfg.max_inflight, graph_max_rows=cfg.graph_max_rows)
     scorer.fallback, scorer.lowering_opts = cfg.fallback, dict(cfg.lowering_opts())
+    scorer.reason_codes = bool(cfg.reason_codes)
     return scorer
 
 

@@ -12,6 +12,12 @@ and into the reference score the scoring plan would have written. ``transformedV
 Columns reproduce ``models/base.py::_output_column`` (string-typed outputs as their ``schema.lookup``
 encodings). What a family cannot provide raises :class:`NotLowerable` naming the output field.
 
+With ``reason_codes=True`` the ``reasonCode`` fields (rank 1 … 8) of a Scorecard are columns too:
+``ops/csrc/reasons.hip`` ranks the codes of every row on the plan's stream, after ``outputs_kernel``
+has written ``valid``, from the matrix the scorecard's tree kernel read (``runtime/reasons.py``), and
+writes them straight into their columns of the output matrix. Without the switch such a field is
+refused by name, as is ``rank > 1`` of every other feature.
+
 Known difference from the host path: a row that fails the MiningField preparation has NaN in every
 column on the host; on the device such a row is a row without a prediction, so a constant column
 (the probability of an undeclared class) and an expression that maps missing values keep their value.
@@ -61,8 +67,9 @@ class OutputPlan(DevicePlan):
     kind = "outputs"
     supports_direct = False
 
-    def __init__(self, compiled, device, top_k: int = 0, **opts):
+    def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, **opts):
         super().__init__(compiled, device)
+        from ..models.scorecard import ScorecardEvaluator
         from .nn_plans import GemmMlpPlan, MlpPlan
         from .plans import ClusterPlan, LinearPlan, TreePlan
         from .segmented import SegmentedPlan, _index_outputs, probs_width
@@ -72,6 +79,16 @@ class OutputPlan(DevicePlan):
             raise ValueError(f"top_k must be in [0, {K.MAX_TOP_K}], got {top_k}")
         self.top_k = top_k
         ev = compiled.evaluator
+        # reasonCode fields of a scorecard rank on the device (ops/csrc/reasons.hip); off: refused by name
+        self._rank_reasons = bool(reason_codes) and isinstance(ev, ScorecardEvaluator)
+        self.reasons = None  # the packed scorecard (ops.reasons.ReasonTables) when a reason kernel runs
+        self._reason_prep = None
+        if self._rank_reasons and ev.scorecard.use_reason_codes:
+            from .reasons import check_baselines
+
+            asked = [of for of in compiled.model.output if of.feature == "reasonCode"]
+            if asked:  # the oracle raises on every batch, the probe below included
+                check_baselines(ev.scorecard, asked[0])
         # what the oracle's result holds for this model: one all-missing row through it
         probe = ev.evaluate(compiled.columns(np.full((1, compiled.n_features), np.nan)))
         self.result_kind = probe.kind
@@ -124,6 +141,7 @@ class OutputPlan(DevicePlan):
 
     # ------------------------------------------------------------------ lowering
     def _lower(self, compiled, ev, probe, base, C: Optional[int], cluster: bool) -> None:
+        from ..ops import reasons as R
         from .derive import _expr_fields
         from .segmented import expression_program
 
@@ -134,6 +152,7 @@ class OutputPlan(DevicePlan):
         self.names = [of.name for of in compiled.model.output]
         self.kernel_names: List[str] = []  # the kernel's columns, in order
         exprs = []
+        reason_fields = []  # (Output field, its column of the matrix): written by the reason kernel
         need_probs = self.top_k > 0
         need_aff = False
         custom = type(ev)._output_column is not ModelEvaluator._output_column
@@ -150,6 +169,15 @@ class OutputPlan(DevicePlan):
             feat = of.feature
             if self._no_index:
                 raise no(of, self._no_index)
+            if self._rank_reasons and feat == "reasonCode":
+                if int(of.rank) > R.MAX_RANK:
+                    raise no(of, f"reason code rank {of.rank} > {R.MAX_RANK}")
+                if ev.scorecard.use_reason_codes:
+                    reason_fields.append((of, self.names.index(of.name)))
+                    continue
+                prog.append((K.OP_NAN, 0, 0))  # useReasonCodes="false": no codes, as the oracle
+                self.kernel_names.append(of.name)
+                continue
             if int(getattr(of, "rank", 1) or 1) > 1:
                 raise no(of, f"rank {of.rank} > 1 is not evaluated")
             if custom and feat in ("reasonCode", "ruleValue", "entityId"):
@@ -227,6 +255,8 @@ class OutputPlan(DevicePlan):
         self.kernel_dst = [pos[n] for n in self.kernel_names[: self.n_named]] + \
             list(range(len(self.names), self.width))
         self.direct_out = not exprs and self.kernel_dst == list(range(self.width)) and self.width == self.n_col
+        if reason_fields:
+            self._lower_reasons(compiled, ev, reason_fields)
         self.expr = None
         if exprs:
             used: List[str] = []
@@ -251,6 +281,32 @@ class OutputPlan(DevicePlan):
                          [pos[of.name] for of, _ in exprs])
             self.expr_inputs = [compiled.active_fields.index(f) for f in inputs]
         self._dst = None
+
+    def _lower_reasons(self, compiled, ev, reason_fields) -> None:
+        """The reason kernel reads the matrix the scorecard's general tree kernel reads: the raw
+        rows with this plan's FieldPrep, or the tile the inner derive pass writes."""
+        from .derive import DerivedPlan
+        from .plans import TreePlan
+        from .reasons import lower_reasons
+
+        tree = self.inner.inner if isinstance(self.inner, DerivedPlan) else self.inner
+        if not isinstance(tree, TreePlan) or tree.layout != "general":
+            raise NotLowerable(f"output {reason_fields[0][0].name!r}: reason codes need the general tree plan, "
+                               f"not {type(tree).__name__}")
+        view = tree.compiled
+        index = getattr(view, "field_index", None) or {f: i for i, f in enumerate(view.active_fields)}
+        self.reasons = lower_reasons(ev.scorecard, compiled.schema, index, int(tree.n_features), reason_fields,
+                                     self.width)
+        self._reason_prep = tree.prep  # None behind a derive pass: the tile is prepared
+
+    def _reason_matrix_host(self, Xn: np.ndarray) -> np.ndarray:
+        """Dry run: the reason kernel's input for the raw fp32 rows ``Xn``."""
+        from .derive import DerivedPlan, emulate
+
+        if isinstance(self.inner, DerivedPlan):
+            P, _ = self.compiled.prepare(Xn)
+            return emulate(self.inner.program, P)
+        return Xn
 
     # ------------------------------------------------------------------ execution
     def alloc_matrix(self, n: int):
@@ -299,6 +355,14 @@ class OutputPlan(DevicePlan):
                     res = run_expression_program(self.device, self.lib, self.expr, Xa.contiguous(), st)
                     for j, c in enumerate(self.expr[4]):
                         outputs[:, c] = res[:, j]
+            if self.reasons is not None:
+                from ..ops.reasons import reasons_launch
+                from .derive import DerivedPlan
+
+                # after outputs_kernel wrote ``valid``; a derive pass left its tile in this stream's buffer
+                Xr = self.inner._buffers(st, n)[0] if isinstance(self.inner, DerivedPlan) else X
+                reasons_launch(Xr, valid if valid is not None else raw_v, outputs, self.reasons,
+                               prep=self._reason_prep, stream=st)
             if score2 is not None:
                 score2.copy_(score)
                 valid2.copy_(valid)
@@ -347,6 +411,11 @@ class OutputPlan(DevicePlan):
             res = emulate(self.expr[0], Xa)
             for j, c in enumerate(self.expr[4]):
                 full[:, c] = res[:, j]
+        if self.reasons is not None:
+            from ..ops.reasons import reasons_numpy
+
+            prep = self._reason_prep.numpy() if self._reason_prep is not None else None
+            reasons_numpy(self._reason_matrix_host(Xn), v, full, self.reasons, prep=prep)
         for dst, src in ((score, s), (valid, v), (outputs, full), (score2, s), (valid2, v)):
             if dst is not None:
                 (dst.numpy() if hasattr(dst, "numpy") else dst)[...] = src
