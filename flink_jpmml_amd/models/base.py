@@ -58,6 +58,60 @@ class ModelResult:
         return out
 
 
+MAX_ENTITY_RANK = 32  # ranks a clustering result keeps (a k-NN result keeps its k neighbours)
+
+
+@dataclass
+class RankedEntities:
+    """Per row, the entities of a clustering or k-NN result ranked by the model's measure:
+    ascending distance / descending similarity, ties to the lower entity index, NaN last.
+
+    ``index`` int64 ``[n, R]`` and ``affinity`` float64 ``[n, R]`` (the finished distance or
+    similarity) hold the first ``R`` ranks: ``min(K, 32)`` of a ClusteringModel, the ``k``
+    neighbours of a NearestNeighborModel. ``ids`` are the entity ids (cluster ids, training instance
+    ids), ``valid`` the rows with a result."""
+
+    index: np.ndarray
+    affinity: np.ndarray
+    ids: List[str]
+    valid: np.ndarray
+
+    @property
+    def width(self) -> int:
+        return int(self.index.shape[1])
+
+    def at(self, rank: int):
+        """``(entity index int64 [n], ok bool [n])`` of 1-based ``rank``: not ok on rows without a
+        result, where the entry's affinity is not finite, and past the list."""
+        n = len(self.valid)
+        if rank > self.width:
+            return np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
+        ok = np.asarray(self.valid, dtype=bool) & np.isfinite(self.affinity[:, rank - 1])
+        return np.where(ok, self.index[:, rank - 1], 0), ok
+
+
+def rank_entities(D: np.ndarray, similarity: bool, width: int):
+    """The first ``width`` ranks of the ``[n, K]`` float64 measure ``D``: ``(index, affinity)``.
+    One stable argsort, as ``NearestNeighborEvaluator._evaluate``; its first column is the
+    ``argmin`` / ``argmax`` of ``ClusteringEvaluator._evaluate``."""
+    key = np.where(np.isnan(D), np.inf, -D if similarity else D)
+    order = np.argsort(key, axis=1, kind="stable")[:, :width]
+    return order, np.take_along_axis(D, order, axis=1)
+
+
+def ranked_entities(res: "ModelResult") -> Optional[RankedEntities]:
+    """The ranked entities of a clustering result (from its ``[n, K]`` measure, on first use) or of
+    a k-NN result (the ``[n, k]`` lists its evaluator left in ``extra``); None for any other model."""
+    got = res.extra.get("ranked")
+    if got is None and res.kind == "clustering" and res.entity_affinities is not None and res.entity_ids is not None \
+            and "similarity" in res.extra:
+        D = np.asarray(res.entity_affinities, dtype=np.float64)
+        index, aff = rank_entities(D, bool(res.extra["similarity"]), min(D.shape[1], MAX_ENTITY_RANK))
+        got = res.extra["ranked"] = RankedEntities(index, aff, list(res.entity_ids),
+                                                   np.asarray(res.valid, dtype=bool))
+    return got
+
+
 class ModelEvaluator:
     """Base class: schema bookkeeping, targets, outputs."""
 
@@ -185,6 +239,10 @@ class ModelEvaluator:
                     return np.zeros(n)
                 p = res.probs[:, res.categories.index(of.value)]
             return np.where(res.valid, p, NAN)
+        if feat in ("entityId", "clusterId", "affinity", "clusterAffinity", "entityAffinity"):
+            col = self._ranked_column(of, res, n)
+            if col is not None:
+                return col
         if feat in ("entityId", "clusterId"):
             if res.kind == "clustering":
                 if feat == "clusterId":
@@ -211,6 +269,36 @@ class ModelEvaluator:
         if feat in ("warning", "reasonCode", "ruleValue", "residual", "standardError", "confidence"):
             return np.full(n, NAN)
         raise UnsupportedFeatureException(f"output feature {feat!r} not supported")
+
+    def _ranked_column(self, of: ir.OutputField, res: ModelResult, n: int) -> Optional[np.ndarray]:
+        """An entity id / affinity column that needs the ranked entities of a clustering or k-NN
+        result: any rank of a k-NN model, ``rank > 1`` and the affinity of a named cluster of a
+        ClusteringModel. None: not such a column (rank 1 of a clustering result, another model)."""
+        feat = of.feature
+        ids = feat in ("entityId", "clusterId")
+        rank = max(1, int(getattr(of, "rank", 1) or 1))
+        clustering = res.kind == "clustering" and "similarity" in res.extra
+        if clustering and not ids and of.value is not None and of.value in res.entity_ids:
+            return np.where(res.valid, res.entity_affinities[:, res.entity_ids.index(of.value)], NAN)
+        if clustering and rank == 1:
+            return None
+        ranked = ranked_entities(res)
+        if ranked is None:
+            return None
+        if not ids and of.value is not None and of.value in ranked.ids:
+            raise UnsupportedFeatureException(
+                f"output {of.name!r}: {feat} of the named training instance {of.value!r} is not kept "
+                f"(only the k nearest are)")
+        idx, ok = ranked.at(rank)
+        if not ok.any():
+            return np.full(n, NAN)
+        if not ids:
+            return np.where(ok, ranked.affinity[:, rank - 1], NAN)
+        if feat == "clusterId":
+            codes = np.arange(1, len(ranked.ids) + 1, dtype=np.float64)
+        else:
+            codes = np.array([self.schema.lookup(of.name, x) for x in ranked.ids], dtype=np.float64)
+        return np.where(ok, codes[idx], NAN)
 
     def decode_outputs(self, out: Dict[str, np.ndarray], row: int) -> Dict[str, Any]:
         return {k: self.schema.decode(k, float(v[row])) for k, v in out.items()}

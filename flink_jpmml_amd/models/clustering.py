@@ -149,4 +149,5 @@ class ClusteringEvaluator(ModelEvaluator):
             entity_ids=self.entity_ids,
             affinity=aff,
             entity_affinities=D,
+            extra={"similarity": not self.kind_distance},  # how base.ranked_entities orders D
         )

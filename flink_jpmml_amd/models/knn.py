@@ -22,7 +22,7 @@ import numpy as np
 from ..api.exceptions import UnsupportedFeatureException
 from ..pmml import ir
 from ..pmml.fields import NAN, Columns, FieldSchema
-from .base import ModelResult
+from .base import ModelResult, RankedEntities
 from .clustering import ClusteringEvaluator
 
 _ROW_BLOCK = 2048
@@ -56,10 +56,12 @@ class NearestNeighborEvaluator(ClusteringEvaluator):
         super().__init__(knn_as_clustering(model, schema), schema)
         self.knn = model
         self.model = model  # outputs / targets / transformations of the original element
+        schema.register_model(model)  # the Output fields' types: an entityId decodes to its id string
         self.target = next((t for t in model.targets if t.field is None or t.field == self.target_field), None)
         self.k = max(1, int(model.k))
         self.kind = "classification" if model.function_name == "classification" else "regression"
         self.targets = list(self.entity_ids)  # instance target strings
+        self.instance_ids = list(model.instance_ids)  # what entityId answers (never the targets)
         if self.kind == "classification":
             cats = self.classification_categories()
             for t in self.targets:
@@ -85,6 +87,8 @@ class NearestNeighborEvaluator(ClusteringEvaluator):
             dist[r0: r0 + _ROW_BLOCK] = np.take_along_axis(D, o, axis=1)
         valid = np.isfinite(dist).all(axis=1) & ~np.all(np.isnan(X), axis=1)
         m = self.knn
+        # the k neighbours and their finished distances / similarities (never an [n, N] matrix)
+        extra = {"ranked": RankedEntities(nn, dist if self.kind_distance else -dist, self.instance_ids, valid)}
         if self.kind == "classification":
             C = len(self.categories)
             votes = np.zeros((n, C))
@@ -102,7 +106,7 @@ class NearestNeighborEvaluator(ClusteringEvaluator):
             with np.errstate(invalid="ignore"):
                 probs = votes / votes.sum(axis=1, keepdims=True)
             return ModelResult("classification", np.where(valid, lab, NAN), valid, categories=self.categories,
-                               probs=np.where(valid[:, None], probs, NAN))
+                               probs=np.where(valid[:, None], probs, NAN), extra=extra)
         y = self.inst_value[nn]
         meth = m.continuous_method
         if meth == "average":
@@ -115,7 +119,7 @@ class NearestNeighborEvaluator(ClusteringEvaluator):
                 v = (w * y).sum(axis=1) / w.sum(axis=1)
         else:
             raise UnsupportedFeatureException(f"continuousScoringMethod {meth!r}")
-        return ModelResult("regression", np.where(valid, v, NAN), valid & np.isfinite(v))
+        return ModelResult("regression", np.where(valid, v, NAN), valid & np.isfinite(v), extra=extra)
 
 
 def _weights(dist: np.ndarray, threshold: float) -> np.ndarray:

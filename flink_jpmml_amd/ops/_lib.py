@@ -289,7 +289,18 @@ class ReasonArgs(ctypes.Structure):
                 ("shared", c_int), ("feat_lds", c_int), ("rows", c_int), ("n_tables", c_int), ("pad", c_int)]
 
 
+class EntityArgs(ctypes.Structure):
+    """entities.hip EntityArgs: a distance model, the rows its plan scored -> their ranked entities."""
+    _fields_ = [("X", c_void_p), ("prep", c_void_p), ("ent", c_void_p), ("weights", c_void_p), ("scales", c_void_p),
+                ("qweights", c_void_p), ("cfun", c_void_p), ("wc", c_void_p), ("cc", c_void_p), ("cols", c_void_p),
+                ("named", c_void_p), ("tables", c_void_p), ("out", c_void_p), ("n_rows", c_int), ("n_feat", c_int),
+                ("ldx", c_int), ("ldo", c_int), ("n_ent", c_int), ("metric", c_int), ("similarity", c_int),
+                ("k", c_int), ("knn", c_int), ("n_col", c_int), ("n_tables", c_int), ("rows", c_int), ("Np", c_int),
+                ("Fp", c_int), ("p", c_float), ("pad", c_int)]
+
+
 _ABI = {
+    "pmml_entities_args_size": EntityArgs,
     "pmml_reasons_args_size": ReasonArgs,
     "pmml_outputs_args_size": OutputArgs,
     "pmml_csr_expand_args_size": CsrExpandArgs,
@@ -441,6 +452,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_reasons_launch.restype = c_int
         lib.pmml_reasons_lds_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
         lib.pmml_reasons_lds_bytes.restype = ctypes.c_longlong
+        lib.pmml_entities_launch.argtypes = [c_void_p, ctypes.POINTER(EntityArgs)]
+        lib.pmml_entities_launch.restype = c_int
+        lib.pmml_entities_lds_bytes.argtypes = [c_int, c_int, c_int]
+        lib.pmml_entities_lds_bytes.restype = ctypes.c_longlong
         _lib = lib
         return lib
 

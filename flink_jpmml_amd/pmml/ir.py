@@ -620,6 +620,17 @@ class NearestNeighborModel(Model):
     inputs: List[KNNInput] = field(default_factory=list)
     instance_fields: Dict[str, str] = field(default_factory=dict)  # field -> InlineTable column
     rows: List[Dict[str, str]] = field(default_factory=list)       # InlineTable rows
+    instance_id_variable: Optional[str] = None  # TrainingInstances/@instanceIdVariable
+
+    @property
+    def instance_ids(self) -> List[str]:
+        """The id of every training instance: the text of the ``instanceIdVariable`` column
+        (through ``InstanceFields``), or its 1-based row number as a string without one."""
+        var = self.instance_id_variable
+        if not var:
+            return [str(i + 1) for i in range(len(self.rows))]
+        col = self.instance_fields.get(var, var)
+        return [r.get(col, "") for r in self.rows]
 
 
 # association rules ---------------------------------------------------------------

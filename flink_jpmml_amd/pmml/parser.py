@@ -687,6 +687,7 @@ def _parse_knn(el: ET.Element) -> ir.NearestNeighborModel:
     ti = _child(el, "TrainingInstances")
     if ti is None:
         raise PmmlParseError("NearestNeighborModel without TrainingInstances")
+    m.instance_id_variable = ti.get("instanceIdVariable") or None
     inf = _child(ti, "InstanceFields")
     for f in _children(inf, "InstanceField") if inf is not None else []:
         m.instance_fields[f.get("field")] = f.get("column") or f.get("field")

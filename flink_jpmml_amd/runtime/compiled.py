@@ -119,17 +119,20 @@ class CompiledPmml:
         return s, v, cols
 
     # ------------------------------------------------------------------ device
-    def output_plan(self, device: Any = "cuda", top_k: int = 0, reason_codes: bool = False, **opts):
+    def output_plan(self, device: Any = "cuda", top_k: int = 0, reason_codes: bool = False,
+                    entity_ranks: bool = False, **opts):
         """The :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan` of this model, lowered once per
-        (device, top_k, reason_codes, options) and cached like :meth:`plan`. ``reason_codes`` ranks a
-        Scorecard's ``reasonCode`` fields on the device; other models ignore it."""
+        (device, top_k, reason_codes, entity_ranks, options) and cached like :meth:`plan`.
+        ``reason_codes`` ranks a Scorecard's ``reasonCode`` fields on the device, ``entity_ranks`` the
+        ranked-entity fields of a clustering or k-NN model; other models ignore them."""
         from .outputs import OutputPlan
 
-        key = f"outputs|{device}|{int(top_k)}|{bool(reason_codes)}|{sorted(opts.items())}"
+        key = f"outputs|{device}|{int(top_k)}|{bool(reason_codes)}|{bool(entity_ranks)}|{sorted(opts.items())}"
         with self._lock:
             p = self._plans.get(key)
             if p is None:
-                p = OutputPlan(self, device, top_k=top_k, reason_codes=bool(reason_codes), **opts)
+                p = OutputPlan(self, device, top_k=top_k, reason_codes=bool(reason_codes),
+                               entity_ranks=bool(entity_ranks), **opts)
                 self._plans[key] = p
             return p
 

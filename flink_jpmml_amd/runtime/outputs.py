@@ -18,6 +18,13 @@ has written ``valid``, from the matrix the scorecard's tree kernel read (``runti
 writes them straight into their columns of the output matrix. Without the switch such a field is
 refused by name, as is ``rank > 1`` of every other feature.
 
+With ``entity_ranks=True`` the ranked-entity fields of a model whose plan is a ``ClusterPlan`` or a
+``KnnPlan`` are columns as well: ``entityId`` / ``clusterId`` / affinity of rank 1 … 32, the affinity
+of a named cluster, the neighbours' ids and distances of a k-NN model (``runtime/entities.py``).
+``ops/csrc/entities.hip`` ranks the entities of every row on the plan's stream after
+``outputs_kernel``, from the rows and the tensors the plan's own kernel read, and writes its columns
+straight into the output matrix. Class outputs of a k-NN classifier stay refused by name.
+
 Known difference from the host path: a row that fails the MiningField preparation has NaN in every
 column on the host; on the device such a row is a row without a prediction, so a constant column
 (the probability of an undeclared class) and an expression that maps missing values keep their value.
@@ -67,11 +74,12 @@ class OutputPlan(DevicePlan):
     kind = "outputs"
     supports_direct = False
 
-    def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, **opts):
+    def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, entity_ranks: bool = False,
+                 **opts):
         super().__init__(compiled, device)
         from ..models.scorecard import ScorecardEvaluator
         from .nn_plans import GemmMlpPlan, MlpPlan
-        from .plans import ClusterPlan, LinearPlan, TreePlan
+        from .plans import ClusterPlan, KnnPlan, LinearPlan, TreePlan
         from .segmented import SegmentedPlan, _index_outputs, probs_width
 
         top_k = int(top_k)
@@ -94,6 +102,9 @@ class OutputPlan(DevicePlan):
         self.result_kind = probe.kind
         self.inner = compile_plan(compiled, device, **opts)  # this plan's own: the cached scoring plan stays as is
         base = _base(self.inner)
+        # ranked-entity fields of the distance families rank on the device (ops/csrc/entities.hip)
+        self._rank_entities = bool(entity_ranks) and isinstance(base, (ClusterPlan, KnnPlan))
+        self.entities = None  # ops.entities.EntityTables when an entity kernel runs
         classes = probe.kind in ("classification", "clustering")
         labels: Optional[List[str]] = None
         C = None
@@ -124,6 +135,7 @@ class OutputPlan(DevicePlan):
                 raise NotLowerable("outputs: the plan's label table does not match its classes")
             table = base.table.detach().cpu().numpy().astype(np.float32)
             self.label_table = self._t(np.append(table, np.float32(np.nan)))
+            self.label_values = table
             if isinstance(base, (ClusterPlan, SegmentedPlan)):
                 # their kernels always read the table: the identity table is the index mode
                 base.table = self._t(np.arange(len(labels), dtype=np.float32))
@@ -143,6 +155,7 @@ class OutputPlan(DevicePlan):
     def _lower(self, compiled, ev, probe, base, C: Optional[int], cluster: bool) -> None:
         from ..ops import reasons as R
         from .derive import _expr_fields
+        from .entities import is_entity_field, lower_entities
         from .segmented import expression_program
 
         schema = compiled.schema
@@ -153,6 +166,7 @@ class OutputPlan(DevicePlan):
         self.kernel_names: List[str] = []  # the kernel's columns, in order
         exprs = []
         reason_fields = []  # (Output field, its column of the matrix): written by the reason kernel
+        entity_fields = []  # likewise, written by the entity kernel
         need_probs = self.top_k > 0
         need_aff = False
         custom = type(ev)._output_column is not ModelEvaluator._output_column
@@ -167,6 +181,9 @@ class OutputPlan(DevicePlan):
 
         for of in compiled.model.output:
             feat = of.feature
+            if self._rank_entities and is_entity_field(of, ev):
+                entity_fields.append((of, self.names.index(of.name)))
+                continue
             if self._no_index:
                 raise no(of, self._no_index)
             if self._rank_reasons and feat == "reasonCode":
@@ -186,7 +203,10 @@ class OutputPlan(DevicePlan):
                 exprs.append((of, len(self.kernel_names)))
                 continue
             if feat in ("predictedValue", "predictedDisplayValue"):
-                if probe.kind == "regression":
+                if probe.kind == "regression" and labels is not None:
+                    # a 1-NN regression on ClusterPlan: the raw result is the nearest instance's index
+                    col = (K.OP_TABLE, len(labels), table([float(v) for v in self.label_values] + [np.nan]))
+                elif probe.kind == "regression":
                     col = (K.OP_VALUE, 0, 0)
                 elif labels is not None:
                     col = (K.OP_TABLE, len(labels), table([schema.lookup(of.name, x) for x in labels] + [np.nan]))
@@ -257,6 +277,11 @@ class OutputPlan(DevicePlan):
         self.direct_out = not exprs and self.kernel_dst == list(range(self.width)) and self.width == self.n_col
         if reason_fields:
             self._lower_reasons(compiled, ev, reason_fields)
+        if entity_fields:
+            if self.inner is not base:
+                raise no(entity_fields[0][0], f"entity ranks need the rows {type(base).__name__} reads, "
+                                              f"not those of a {type(self.inner).__name__}")
+            self.entities = lower_entities(base, ev, schema, entity_fields, self.width)
         self.expr = None
         if exprs:
             used: List[str] = []
@@ -363,6 +388,10 @@ class OutputPlan(DevicePlan):
                 Xr = self.inner._buffers(st, n)[0] if isinstance(self.inner, DerivedPlan) else X
                 reasons_launch(Xr, valid if valid is not None else raw_v, outputs, self.reasons,
                                prep=self._reason_prep, stream=st)
+            if self.entities is not None:
+                from ..ops.entities import entities_launch
+
+                entities_launch(X, outputs, self.entities, prep=self.inner.prep, stream=st)
             if score2 is not None:
                 score2.copy_(score)
                 valid2.copy_(valid)
@@ -379,6 +408,10 @@ class OutputPlan(DevicePlan):
         v = np.asarray(res.value, dtype=np.float64)
         valid = np.asarray(res.valid, dtype=bool) & okp & ~np.isnan(v)
         probs = None
+        if self.labels is not None and self.result_kind == "regression":  # 1-NN on ClusterPlan: the index
+            from ..models.base import ranked_entities
+
+            v = np.where(valid, ranked_entities(res).index[:, 0], np.nan)
         if self.labels is not None and self.result_kind == "classification" and res.categories is not None \
                 and list(res.categories) != self.labels:
             to_plan = np.array([self.labels.index(x) if x in self.labels else -1 for x in res.categories] + [-1])
@@ -416,6 +449,11 @@ class OutputPlan(DevicePlan):
 
             prep = self._reason_prep.numpy() if self._reason_prep is not None else None
             reasons_numpy(self._reason_matrix_host(Xn), v, full, self.reasons, prep=prep)
+        if self.entities is not None:
+            from ..ops.entities import entities_numpy
+
+            prep = self.inner.prep.numpy() if self.inner.prep is not None else None
+            entities_numpy(Xn, full, self.entities, prep=prep)
         for dst, src in ((score, s), (valid, v), (outputs, full), (score2, s), (valid2, v)):
             if dst is not None:
                 (dst.numpy() if hasattr(dst, "numpy") else dst)[...] = src
