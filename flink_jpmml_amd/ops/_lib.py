@@ -210,7 +210,7 @@ class KnnArgs(ctypes.Structure):
                 ("qweights", c_void_p), ("cfun", c_void_p), ("inst_value", c_void_p), ("inst_class", c_void_p),
                 ("class_table", c_void_p), ("metric", c_int), ("similarity", c_int), ("p", c_float), ("k", c_int),
                 ("agg", c_int), ("threshold", c_float), ("epi", Epilogue), ("score", c_void_p),
-                ("valid", c_void_p)]
+                ("valid", c_void_p), ("probs", c_void_p), ("n_class", c_int)]
 
 
 class GemmArgs(ctypes.Structure):

@@ -18,6 +18,14 @@
 // instance distances of one row per 32-instance tile and feeds them into its own top-k; the two
 // half-waves' lists of a row are merged through lane^32 shuffles. Rows with a missing value redo
 // the exact form in the same wave.
+//
+// Class outputs (CLASSES = true, picked when KnnArgs::probs is set): the same vote also leaves the
+// winner as a class index (class_table null) and every class's vote share in probs [rows][n_class].
+// The workgroup first zeroes its contiguous slice of probs with coalesced 16-byte stores; after the
+// staging barriers each lane scatters the <= k non-zero shares of its row from the vote loop it runs
+// anyway (a class's total is emitted at the class's first rank), and rows without neighbours are
+// overwritten with NaN by the lanes of their wave together. No barrier is added, so the early
+// returns stay. Nothing loops over n_class per lane.
 #include "common.h"
 #include "distance.h"
 #include "epilogue.h"
@@ -48,11 +56,45 @@ struct KnnArgs {
   Epilogue epi;             // Target stage of a regression value (tgt flags only)
   float* score;
   uint8_t* valid;
+  float* probs;             // [n_rows][n_class] vote shares (class outputs), or null
+  int n_class;
 };
 
-// Aggregate the k nearest (sorted by key) into the row's score / validity.
-template <int KMAX>
-__device__ __forceinline__ void knn_finish(const KnnArgs& a, const float (&key)[KMAX], const int (&id)[KMAX],
+// Class outputs: zero the workgroup's contiguous [rows x n_class] slice of probs (scalar head / tail
+// around the 16-byte aligned body). The staging barriers that follow order it before the scatter.
+__device__ __forceinline__ void zero_probs(const KnnArgs& a, int row0) {
+  const int tid = threadIdx.x;
+  float* base = a.probs + (size_t)row0 * a.n_class;
+  const int total = min(TB, a.n_rows - row0) * a.n_class;  // <= 256 * 256
+  const int head = min(total, (int)((16 - (reinterpret_cast<uintptr_t>(base) & 15)) & 15) >> 2);
+  const int n4 = (total - head) >> 2;
+  float4* body = reinterpret_cast<float4*>(base + head);
+  if (tid < head) base[tid] = 0.f;
+  for (int q = tid; q < n4; q += TB) body[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int tail = head + 4 * n4 + tid;
+  if (tail < total) base[tail] = 0.f;
+}
+
+// Class outputs: NaN in every column of the rows in `mask` (bit b = row rbase + b), a wave-uniform
+// ballot of the lanes that call this together. Those lanes (any subset of the wave: lanes past
+// n_rows and the MFMA kernel's upper half-wave have returned) share each row's columns by their
+// rank among themselves, so no barrier and no returned lane is needed.
+__device__ __forceinline__ void nan_rows(const KnnArgs& a, unsigned long long mask, int rbase) {
+  const unsigned long long active = __ballot(true);
+  const int n_active = __popcll(active);
+  const int rank = __popcll(active & ((1ull << (threadIdx.x & 63)) - 1));
+  while (mask) {
+    const int b = __ffsll(mask) - 1;
+    mask &= mask - 1;
+    float* p = a.probs + (size_t)(rbase + b) * a.n_class;
+    for (int c = rank; c < a.n_class; c += n_active) p[c] = __builtin_nanf("");
+  }
+}
+
+// Aggregate the k nearest (sorted by key) into the row's score / validity. CLASSES: also the row's
+// vote shares; returns whether the row voted (its neighbours are valid).
+template <int KMAX, bool CLASSES = false>
+__device__ __forceinline__ bool knn_finish(const KnnArgs& a, const float (&key)[KMAX], const int (&id)[KMAX],
                                            float adj, bool ok, int row) {
   const int k = a.k;
   float d[KMAX];
@@ -64,6 +106,7 @@ __device__ __forceinline__ void knn_finish(const KnnArgs& a, const float (&key)[
     if (j < k) ok = ok && __builtin_isfinite(d[j]) && id[j] >= 0 && id[j] < a.n_inst;
   }
   float s = __builtin_nanf("");
+  const bool voted = ok;
   if (ok) {
     if (a.agg == AGG_MAJORITY || a.agg == AGG_WMAJORITY) {
       int cls[KMAX];
@@ -84,20 +127,38 @@ __device__ __forceinline__ void knn_finish(const KnnArgs& a, const float (&key)[
       // names the winner (= the tied class whose best member ranks first)
       float best = -1.f;
       int best_c = -1;
+      [[maybe_unused]] float total = 0.f;  // class outputs: Σ votes, in rank order
+      if constexpr (CLASSES) {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+          if (j < k) total += w[j];
+      }
 #pragma unroll
       for (int j = 0; j < KMAX; ++j) {
         if (j < k) {
           float v = 0.f;
+          [[maybe_unused]] bool first = true;  // no better-ranked neighbour of this class
 #pragma unroll
-          for (int i = 0; i < KMAX; ++i)
-            if (i < k && cls[i] == cls[j]) v += w[i];
+          for (int i = 0; i < KMAX; ++i) {
+            if (i < k && cls[i] == cls[j]) {
+              v += w[i];
+              if constexpr (CLASSES) first = first && i >= j;
+            }
+          }
           if (v > best) {
             best = v;
             best_c = cls[j];
           }
+          if constexpr (CLASSES) {  // a class's share is emitted once, at its first rank
+            if (first && (unsigned)cls[j] < (unsigned)a.n_class)
+              a.probs[(size_t)row * a.n_class + cls[j]] = v / total;
+          }
         }
       }
-      s = best_c >= 0 ? a.class_table[best_c] : __builtin_nanf("");
+      if constexpr (CLASSES)  // no table: the winner's index (the index mode of the output plans)
+        s = best_c < 0 ? __builtin_nanf("") : a.class_table ? a.class_table[best_c] : (float)best_c;
+      else
+        s = best_c >= 0 ? a.class_table[best_c] : __builtin_nanf("");
       ok = s == s;
     } else {
       float y[KMAX];
@@ -156,14 +217,16 @@ __device__ __forceinline__ void knn_finish(const KnnArgs& a, const float (&key)[
   }
   a.score[row] = ok ? s : __builtin_nanf("");
   a.valid[row] = ok ? 1 : 0;
+  return voted;
 }
 
-template <int METRIC, int KMAX>
+template <int METRIC, int KMAX, bool CLASSES>
 __global__ __launch_bounds__(TB) void knn_kernel(KnnArgs a) {
   extern __shared__ __align__(16) uint32_t smem[];
   float* feat = reinterpret_cast<float*>(smem);
   int* bad = reinterpret_cast<int*>(smem + a.n_feat * TB);
   const int row0 = blockIdx.x * TB;
+  if constexpr (CLASSES) zero_probs(a, row0);
   stage_rows_T<TB>(a.X, a.n_rows, a.n_feat, a.ldx, a.prep, feat, bad, row0);
   const int tid = threadIdx.x;
   const int row = row0 + tid;
@@ -188,19 +251,20 @@ __global__ __launch_bounds__(TB) void knn_kernel(KnnArgs a) {
       worst = kth<KMAX>(key, a.k);
     }
   }
-  knn_finish<KMAX>(a, key, id, adj, bad[tid] == 0 && qpresent > 0.f, row);
+  const bool voted = knn_finish<KMAX, CLASSES>(a, key, id, adj, bad[tid] == 0 && qpresent > 0.f, row);
+  if constexpr (CLASSES) nan_rows(a, __ballot(!voted), row0 + (tid & ~63));
 }
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 // One row of the MFMA kernel: keep the expansion's top-k, or redo it exactly for a row with a
 // missing value (skip missing fields, rescale by Σq / Σq_present).
-template <int KMAX>
-__device__ __forceinline__ void mfma_row_finish(const KnnArgs& a, const float* feat, const int* bad,
+template <int KMAX, bool CLASSES>
+__device__ __forceinline__ bool mfma_row_finish(const KnnArgs& a, const float* feat, const int* bad,
                                                 float (&key)[KMAX], int (&id)[KMAX], bool missing, int rl,
                                                 int row0) {
   const int row = row0 + rl;
-  if (row >= a.n_rows) return;
+  if (row >= a.n_rows) return true;
   float qpresent = 1.f, adj = 1.f;
   if (missing) {
     adj = row_adjust(a, feat + rl, TB, &qpresent);
@@ -218,16 +282,17 @@ __device__ __forceinline__ void mfma_row_finish(const KnnArgs& a, const float* f
       }
     }
   }
-  knn_finish<KMAX>(a, key, id, adj, bad[rl] == 0 && qpresent > 0.f, row);
+  return knn_finish<KMAX, CLASSES>(a, key, id, adj, bad[rl] == 0 && qpresent > 0.f, row);
 }
 
-template <int KMAX>
+template <int KMAX, bool CLASSES>
 __global__ __launch_bounds__(TB) void knn_mfma_kernel(KnnArgs a, const float* __restrict__ wc,
                                                       const float* __restrict__ cc, int Np, int Fp) {
   extern __shared__ __align__(16) uint32_t smem[];
   float* feat = reinterpret_cast<float*>(smem);
   int* bad = reinterpret_cast<int*>(smem + a.n_feat * TB);
   const int row0 = blockIdx.x * TB;
+  if constexpr (CLASSES) zero_probs(a, row0);
   stage_rows_T<TB>(a.X, a.n_rows, a.n_feat, a.ldx, a.prep, feat, bad, row0);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -302,21 +367,35 @@ __global__ __launch_bounds__(TB) void knn_mfma_kernel(KnnArgs a, const float* __
     }
   }
   if (half != 0) return;
-  mfma_row_finish<KMAX>(a, feat, bad, key0, id0, missing[0], rb, row0);
-  mfma_row_finish<KMAX>(a, feat, bad, key1, id1, missing[1], rb + 32, row0);
+  const bool v0 = mfma_row_finish<KMAX, CLASSES>(a, feat, bad, key0, id0, missing[0], rb, row0);
+  const bool v1 = mfma_row_finish<KMAX, CLASSES>(a, feat, bad, key1, id1, missing[1], rb + 32, row0);
+  if constexpr (CLASSES) {  // the lower half-wave's bit b: rows wave * 64 + b and + 32 + b
+    nan_rows(a, __ballot(!v0), row0 + wave * 64);
+    nan_rows(a, __ballot(!v1), row0 + wave * 64 + 32);
+  }
 }
 
-template <int KMAX>
+template <int KMAX, bool CLASSES>
 int launch_valu(hipStream_t stream, const KnnArgs& a, dim3 grid, size_t lds) {
   switch (a.metric) {
-    case M_SQEUCLID: hipLaunchKernelGGL((knn_kernel<M_SQEUCLID, KMAX>), grid, dim3(TB), lds, stream, a); break;
-    case M_EUCLID: hipLaunchKernelGGL((knn_kernel<M_EUCLID, KMAX>), grid, dim3(TB), lds, stream, a); break;
-    case M_CITY: hipLaunchKernelGGL((knn_kernel<M_CITY, KMAX>), grid, dim3(TB), lds, stream, a); break;
-    case M_CHEBY: hipLaunchKernelGGL((knn_kernel<M_CHEBY, KMAX>), grid, dim3(TB), lds, stream, a); break;
-    case M_MINKOWSKI: hipLaunchKernelGGL((knn_kernel<M_MINKOWSKI, KMAX>), grid, dim3(TB), lds, stream, a); break;
+    case M_SQEUCLID:
+      hipLaunchKernelGGL((knn_kernel<M_SQEUCLID, KMAX, CLASSES>), grid, dim3(TB), lds, stream, a);
+      break;
+    case M_EUCLID: hipLaunchKernelGGL((knn_kernel<M_EUCLID, KMAX, CLASSES>), grid, dim3(TB), lds, stream, a); break;
+    case M_CITY: hipLaunchKernelGGL((knn_kernel<M_CITY, KMAX, CLASSES>), grid, dim3(TB), lds, stream, a); break;
+    case M_CHEBY: hipLaunchKernelGGL((knn_kernel<M_CHEBY, KMAX, CLASSES>), grid, dim3(TB), lds, stream, a); break;
+    case M_MINKOWSKI:
+      hipLaunchKernelGGL((knn_kernel<M_MINKOWSKI, KMAX, CLASSES>), grid, dim3(TB), lds, stream, a);
+      break;
     default: return -6;
   }
   return 0;
+}
+
+template <int KMAX, bool CLASSES>
+void launch_mfma(hipStream_t stream, const KnnArgs& a, dim3 grid, size_t lds, const float* wc, const float* cc,
+                 int Np, int Fp) {
+  hipLaunchKernelGGL((knn_mfma_kernel<KMAX, CLASSES>), grid, dim3(TB), lds, stream, a, wc, cc, Np, Fp);
 }
 }  // namespace
 
@@ -329,16 +408,26 @@ PMML_API int pmml_knn_launch(hipStream_t stream, const KnnArgs* args, const floa
   const KnnArgs a = *args;
   if (a.n_rows <= 0) return 0;
   if (a.n_feat > 128 || a.k < 1 || a.k > 32 || a.k > a.n_inst || a.agg < 0 || a.agg > AGG_WAVERAGE) return -4;
+  const bool classes = a.probs != nullptr;  // class outputs: votes only, at most 256 classes
+  if (classes && (a.agg > AGG_WMAJORITY || a.n_class < 1 || a.n_class > 256)) return -4;
+  if (!classes && a.agg <= AGG_WMAJORITY && !a.class_table) return -4;  // the index mode needs probs
   const size_t lds = (size_t)a.n_feat * TB * 4 + TB * 4;
   dim3 grid((a.n_rows + TB - 1) / TB);
   int rc = 0;
   if (wc) {
     if ((Np & 31) || (Fp & 1) || Fp < a.n_feat || Np < a.n_inst || a.similarity) return -4;
     if (a.metric != M_SQEUCLID && a.metric != M_EUCLID) return -6;
-    if (a.k <= 8) hipLaunchKernelGGL(knn_mfma_kernel<8>, grid, dim3(TB), lds, stream, a, wc, cc, Np, Fp);
-    else hipLaunchKernelGGL(knn_mfma_kernel<32>, grid, dim3(TB), lds, stream, a, wc, cc, Np, Fp);
+    if (a.k <= 8) {
+      if (classes) launch_mfma<8, true>(stream, a, grid, lds, wc, cc, Np, Fp);
+      else launch_mfma<8, false>(stream, a, grid, lds, wc, cc, Np, Fp);
+    } else {
+      if (classes) launch_mfma<32, true>(stream, a, grid, lds, wc, cc, Np, Fp);
+      else launch_mfma<32, false>(stream, a, grid, lds, wc, cc, Np, Fp);
+    }
+  } else if (a.k <= 8) {
+    rc = classes ? launch_valu<8, true>(stream, a, grid, lds) : launch_valu<8, false>(stream, a, grid, lds);
   } else {
-    rc = a.k <= 8 ? launch_valu<8>(stream, a, grid, lds) : launch_valu<32>(stream, a, grid, lds);
+    rc = classes ? launch_valu<32, true>(stream, a, grid, lds) : launch_valu<32, false>(stream, a, grid, lds);
   }
   if (rc) return rc;
   return hipGetLastError() == hipSuccess ? 0 : -7;

@@ -259,6 +259,7 @@ class StreamingScorer:
         self.lowering_opts: dict = {}
         self.reason_codes = False  # ScoringConfig.reason_codes: passed to output_plan only
         self.entity_ranks = False  # ScoringConfig.entity_ranks: likewise
+        self.knn_classes = False  # ScoringConfig.knn_classes: likewise
         self._row_state = None  # score_row's persistent buffers
         self._row_lock = threading.Lock()  # ...shared by every caller of score_row
         from ..ops import _lib
@@ -469,7 +470,8 @@ class StreamingScorer:
                 "without it (bind the model from its document on this rank)")
         try:
             return compiled.output_plan(self.device, top_k=top_k, reason_codes=self.reason_codes,
-                                        entity_ranks=self.entity_ranks, **self.lowering_opts)
+                                        entity_ranks=self.entity_ranks, knn_classes=self.knn_classes,
+                                        **self.lowering_opts)
         except NotLowerable as e:
             if self.fallback == "error":
                 raise
@@ -845,6 +847,7 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
     scorer.fallback, scorer.lowering_opts = cfg.fallback, dict(cfg.lowering_opts())
     scorer.reason_codes = bool(cfg.reason_codes)
     scorer.entity_ranks = bool(cfg.entity_ranks)
+    scorer.knn_classes = bool(cfg.knn_classes)
     return scorer
 
 

@@ -23,7 +23,19 @@ With ``entity_ranks=True`` the ranked-entity fields of a model whose plan is a `
 of a named cluster, the neighbours' ids and distances of a k-NN model (``runtime/entities.py``).
 ``ops/csrc/entities.hip`` ranks the entities of every row on the plan's stream after
 ``outputs_kernel``, from the rows and the tensors the plan's own kernel read, and writes its columns
-straight into the output matrix. Class outputs of a k-NN classifier stay refused by name.
+straight into the output matrix. Class outputs of a k-NN classifier stay refused by name unless
+``knn_classes=True``.
+
+With ``knn_classes=True`` the class outputs of a k-NN classifier are columns too. For ``k > 1`` the
+inner ``KnnPlan`` runs in index mode (``class_table = None``): the class-output instantiation of
+``ops/csrc/knn.hip`` writes the winning class index and the ``[rows, C]`` vote shares
+(``votes_c / Σ votes``; NaN in a row without a prediction), and ``predictedValue`` /
+``predictedDisplayValue``, ``probability`` (winner, named class) and ``top_k`` are the ordinary
+column ops over them. A 1-NN classifier stays on ``ClusterPlan`` (the raw result is the nearest
+instance's index): its ``probability`` columns are tables over the instances holding 1 / 0;
+``top_k`` needs the matrix and is refused for it. More than 256 classes are refused naming the first
+class field. Entity fields of the same document still go to the entity kernel (``entity_ranks=True``)
+or are refused by name.
 
 Known difference from the host path: a row that fails the MiningField preparation has NaN in every
 column on the host; on the device such a row is a row without a prediction, so a constant column
@@ -75,7 +87,7 @@ class OutputPlan(DevicePlan):
     supports_direct = False
 
     def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, entity_ranks: bool = False,
-                 **opts):
+                 knn_classes: bool = False, **opts):
         super().__init__(compiled, device)
         from ..models.scorecard import ScorecardEvaluator
         from .nn_plans import GemmMlpPlan, MlpPlan
@@ -109,6 +121,23 @@ class OutputPlan(DevicePlan):
         labels: Optional[List[str]] = None
         C = None
         self._affinity = False
+        # class outputs of a k-NN classifier: the vote kernel's index mode (k > 1), tables over the
+        # instances (k = 1 on ClusterPlan)
+        knn_votes = bool(knn_classes) and getattr(ev, "knn", None) is not None and probe.kind == "classification"
+        self._knn_one = knn_votes and isinstance(base, ClusterPlan)
+        self._knn_index = False
+        if knn_votes and isinstance(base, KnnPlan) and base.labels is not None:
+            if len(base.labels) > K.MAX_CLASSES:
+                asked = [of for of in compiled.model.output
+                         if of.feature in ("predictedValue", "predictedDisplayValue", "probability")]
+                if asked:
+                    raise NotLowerable(f"output {asked[0].name!r}: {len(base.labels)} classes > {K.MAX_CLASSES}")
+                if top_k:
+                    raise NotLowerable(f"top_k: {len(base.labels)} classes > {K.MAX_CLASSES}")
+            else:
+                labels = list(base.labels)
+                C = len(labels)
+                self._knn_index = True
         if isinstance(base, ClusterPlan):
             labels = list(ev.entity_ids)
         elif isinstance(base, (LinearPlan, TreePlan)):
@@ -131,12 +160,15 @@ class OutputPlan(DevicePlan):
         self.labels = labels
         self.label_table = None
         if labels is not None:
-            if getattr(base, "table", None) is None or int(base.table.numel()) != len(labels):
+            own = base.class_table if self._knn_index else getattr(base, "table", None)
+            if own is None or int(own.numel()) != len(labels):
                 raise NotLowerable("outputs: the plan's label table does not match its classes")
-            table = base.table.detach().cpu().numpy().astype(np.float32)
+            table = own.detach().cpu().numpy().astype(np.float32)
             self.label_table = self._t(np.append(table, np.float32(np.nan)))
             self.label_values = table
-            if isinstance(base, (ClusterPlan, SegmentedPlan)):
+            if self._knn_index:
+                base.class_table = None  # the vote kernel's index mode
+            elif isinstance(base, (ClusterPlan, SegmentedPlan)):
                 # their kernels always read the table: the identity table is the index mode
                 base.table = self._t(np.arange(len(labels), dtype=np.float32))
                 if isinstance(base, SegmentedPlan):
@@ -167,7 +199,7 @@ class OutputPlan(DevicePlan):
         exprs = []
         reason_fields = []  # (Output field, its column of the matrix): written by the reason kernel
         entity_fields = []  # likewise, written by the entity kernel
-        need_probs = self.top_k > 0
+        need_probs = self.top_k > 0 or self._knn_index  # the vote kernel's index mode always writes its shares
         need_aff = False
         custom = type(ev)._output_column is not ModelEvaluator._output_column
 
@@ -215,6 +247,17 @@ class OutputPlan(DevicePlan):
             elif feat == "probability":
                 if probe.probs is None or probe.categories is None:
                     raise no(of, "the model has no probabilities")
+                if self._knn_one:
+                    # the nearest instance casts the only vote: 1 for its class, 0 for every other
+                    if of.value is None:
+                        col = (K.OP_TABLE, len(labels), table([1.0] * len(labels) + [np.nan]))
+                    elif of.value not in probe.categories:
+                        col = (K.OP_CONST, 0, table([0.0]))
+                    else:
+                        col = (K.OP_TABLE, len(labels), table([float(x == of.value) for x in labels] + [np.nan]))
+                    prog.append(col)
+                    self.kernel_names.append(of.name)
+                    continue
                 if C is None:
                     raise no(of, f"{type(base).__name__} does not expose probabilities")
                 if of.value is None:
@@ -250,6 +293,9 @@ class OutputPlan(DevicePlan):
             prog.append(col)
             self.kernel_names.append(of.name)
         if self.top_k:
+            if self._knn_one:
+                raise NotLowerable("top_k: a 1-NN classifier runs on ClusterPlan, whose result is the nearest "
+                                   "instance and not a vote matrix (top_k of k = 1 is host-only)")
             if C is None:
                 raise NotLowerable(f"top_k: {type(base).__name__} does not expose class probabilities")
             if self.categories != labels:

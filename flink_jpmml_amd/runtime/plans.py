@@ -613,12 +613,16 @@ class KnnPlan(DevicePlan):
     expansion for squared / plain euclidean absDiff distances over many instances), a register
     top-k and the PMML aggregation (vote / average / median / weighted forms) in the same kernel.
     Mirrors :class:`~flink_jpmml_amd.models.knn.NearestNeighborEvaluator`; ``k == 1`` stays a
-    clustering argmin (:class:`ClusterPlan`)."""
+    clustering argmin (:class:`ClusterPlan`).
+
+    Class outputs: ``launch(..., probs=)`` also writes every class's vote share (``[n, C]`` fp32,
+    contiguous rows, ``C = len(labels)``), and with ``class_table = None`` (the index mode of
+    :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan`) the score is the winning class index."""
 
     kind = "knn"
     _STATE = DevicePlan._STATE + ("inst", "weights", "scales", "qweights", "cfun", "inst_value", "inst_class",
                                   "class_table", "metric_code", "similarity", "p", "k", "agg", "threshold",
-                                  "variant", "wc", "cc", "tgt")
+                                  "variant", "wc", "cc", "tgt", "labels")
     _AGG = {"majorityVote": 0, "weightedMajorityVote": 1, "average": 2, "median": 3, "weightedAverage": 4}
     K_MAX = 32
     MFMA_MIN_INSTANCES = 64
@@ -653,11 +657,12 @@ class KnnPlan(DevicePlan):
         if ev.kind == "classification":
             self.inst_class = self._t(np.asarray(ev.inst_class, dtype=np.int32))
             self.class_table = self._t(_label_table(ev.categories))
+            self.labels = list(ev.categories)
             self.inst_value = None
             self.tgt = None
         else:
             self.inst_value = self._t(ev.inst_value.astype(np.float32))
-            self.inst_class = self.class_table = None
+            self.inst_class = self.class_table = self.labels = None
             self.tgt = target_post(ev.target, force=True) if ev.target is not None else None
         mfma_ok = (self.similarity == 0 and self.metric_code in (0, 1) and all(c == "absDiff" for c in ev.compare))
         if knn_variant not in ("auto", "valu", "mfma"):
@@ -688,6 +693,15 @@ class KnnPlan(DevicePlan):
         a.agg, a.threshold = self.agg, self.threshold
         a.epi = _epilogue(0, tgt=self.tgt)
         a.score, a.valid = ptr(score), ptr(valid)
+        if probs is not None:
+            if self.labels is None:
+                raise ValueError("k-NN regression has no class vote shares (probs)")
+            C = len(self.labels)
+            if tuple(probs.shape) != (X.shape[0], C) or not probs.is_contiguous() or probs.dtype != X.dtype:
+                raise ValueError(f"probs must be a contiguous fp32 [{X.shape[0]}, {C}] matrix")
+            a.probs, a.n_class = ptr(probs), C
+        elif self.labels is not None and self.class_table is None:
+            raise ValueError("k-NN index mode (class_table = None) needs probs")
         if self.variant == "mfma":
             Np, Fp = self.wc.shape
             check(self.lib.pmml_knn_launch(stream_handle(stream), ctypes.byref(a), ptr(self.wc), ptr(self.cc),
