@@ -71,6 +71,12 @@ class ScoringConfig:
     and ``top_k``. Off: such a field does not lower, and the Output fields of that model follow
     ``fallback``. Other models ignore it."""
 
+    svm_classes: bool = False
+    """Score the class Output fields of an SVM classifier on the device when a batch is scored with
+    ``outputs=True`` (``FJA_SVM_CLASSES=1``): the predicted label, the machines' vote shares as
+    ``probability`` and ``top_k``. Off: such a field does not lower, and the Output fields of that
+    model follow ``fallback``. Other models ignore it."""
+
     host_threads: int = 0
     """Worker threads of the native host tree walk (``fallback="host"`` models, CPU-only ranks,
     direct CPU ``predict_batch``); 0 = ``FJA_HOST_THREADS`` or 1. Results do not depend on it."""
@@ -173,7 +179,8 @@ class ScoringConfig:
                   host_threads=get("HOST_THREADS", int),
                   reason_codes=get("REASON_CODES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
                   entity_ranks=get("ENTITY_RANKS", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
-                  knn_classes=get("KNN_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")))
+                  knn_classes=get("KNN_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
+                  svm_classes=get("SVM_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")))
         kw = {k: v for k, v in kw.items() if v is not None}
         kw.update({k: v for k, v in overrides.items() if v is not None})
         return ScoringConfig(**kw)

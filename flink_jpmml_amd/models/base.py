@@ -58,6 +58,19 @@ class ModelResult:
         return out
 
 
+def class_probabilities(res: "ModelResult") -> Optional[np.ndarray]:
+    """What the output side reports as a result's class probabilities: ``res.probs``, or for a result
+    that carries machine votes (``extra["vote_shares"]``, an SVM classifier) the shares
+    ``votes_c / Σ votes``, NaN on rows without a prediction; None when the result has neither.
+    Segment aggregation reads ``ModelResult.probs`` itself and does not see the shares."""
+    if res.probs is not None:
+        return res.probs
+    shares = res.extra.get("vote_shares")
+    if shares is None:
+        return None
+    return np.where(np.asarray(res.valid, dtype=bool)[:, None], shares, NAN)
+
+
 MAX_ENTITY_RANK = 32  # ranks a clustering result keeps (a k-NN result keeps its k neighbours)
 
 
@@ -229,15 +242,16 @@ class ModelEvaluator:
                 return np.where(res.valid, res.value, NAN)
             return self._encode_result_labels(of.name, res)
         if feat == "probability":
-            if res.probs is None or res.categories is None:
+            probs = class_probabilities(res)
+            if probs is None or res.categories is None:
                 raise UnsupportedFeatureException(f"output {of.name!r}: model has no probabilities")
             if of.value is None:
                 idx = np.where(res.valid, res.value, 0).astype(np.int64)
-                p = res.probs[np.arange(n), idx]
+                p = probs[np.arange(n), idx]
             else:
                 if of.value not in res.categories:
                     return np.zeros(n)
-                p = res.probs[:, res.categories.index(of.value)]
+                p = probs[:, res.categories.index(of.value)]
             return np.where(res.valid, p, NAN)
         if feat in ("entityId", "clusterId", "affinity", "clusterAffinity", "entityAffinity"):
             col = self._ranked_column(of, res, n)

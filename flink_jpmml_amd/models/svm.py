@@ -104,5 +104,9 @@ class SvmEvaluator(ModelEvaluator):
                 # OneAgainstAll without alternate: the machine votes for its category when it fires
                 votes[first, t] += 1
         lab = np.argmax(votes, axis=1).astype(np.float64)
+        # vote shares (what the output side reports as probabilities, base.class_probabilities): 0/0 = NaN
+        # where no machine voted. ``probs`` stays None: segment aggregation sees what it always saw.
+        with np.errstate(invalid="ignore", divide="ignore"):
+            shares = votes / votes.sum(axis=1, keepdims=True)
         return ModelResult("classification", np.where(valid, lab, NAN), valid.copy(), categories=cats,
-                           probs=None, extra={"votes": votes})
+                           probs=None, extra={"votes": votes, "vote_shares": shares})

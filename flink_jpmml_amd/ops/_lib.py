@@ -252,7 +252,7 @@ class SvmArgs(ctypes.Structure):
                 ("n_in", c_int), ("n_machines", c_int), ("kernel", c_int), ("classification", c_int),
                 ("gamma", c_float), ("coef0", c_float), ("degree", c_float), ("max_wins", c_int),
                 ("n_classes", c_int), ("pad", c_int), ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p),
-                ("decision", c_void_p)]
+                ("decision", c_void_p), ("probs", c_void_p)]
 
 
 class SvmWideArgs(ctypes.Structure):

@@ -8,6 +8,11 @@
 //  * svm_kernel (few support vectors): one lane per row, the row's (prepared) features in
 //    registers (FMAX template bucket, zero padded), every support vector read by all lanes at the
 //    same address (broadcast); machines (<= MMAX) accumulate in registers.
+//
+// Class outputs (CLASSES = true, picked when SvmArgs::probs is set): the lane that finishes a row
+// also writes the row's vote shares votes_c / sum(votes) into probs [rows][n_classes] (one IEEE
+// division each; NaN in a row without a prediction, and 0/0 = NaN where no machine voted), and a
+// null epi.table makes the score the winning class index (the index mode of the output plans).
 #include "epilogue.h"
 
 namespace {
@@ -36,9 +41,12 @@ struct SvmArgs {
   float* score;
   uint8_t* valid;
   float* decision;  // optional [n_rows][n_machines]
+  float* probs;     // [n_rows][n_classes] vote shares (class outputs), or null
 };
 
 // Decision values -> machine votes / regression score, validity, outputs (both kernels).
+// CLASSES: also the row's vote shares, and the winner's index as the score when there is no table.
+template <bool CLASSES = false>
 __device__ __forceinline__ void svm_finish(const SvmArgs& a, int row, const float (&acc)[MMAX], bool ok) {
   if (a.decision) {
     for (int m = 0; m < a.n_machines; ++m) a.decision[(size_t)row * a.n_machines + m] = acc[m];
@@ -61,7 +69,20 @@ __device__ __forceinline__ void svm_finish(const SvmArgs& a, int row, const floa
     int best = 0;
     for (int c = 1; c < a.n_classes && c < 16; ++c)
       if (votes[c] > votes[best]) best = c;
-    sc = a.epi.table[best];
+    if constexpr (CLASSES) {
+      sc = a.epi.table ? a.epi.table[best] : (float)best;
+      const bool voted = ok && (sc == sc);
+      int total = 0;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) total += votes[c];
+      const float ft = (float)total;
+      float* p = a.probs + (size_t)row * a.n_classes;
+#pragma unroll
+      for (int c = 0; c < 16; ++c)
+        if (c < a.n_classes) p[c] = voted ? (float)votes[c] / ft : __builtin_nanf("");
+    } else {
+      sc = a.epi.table[best];
+    }
   }
   ok = ok && (sc == sc);
   if (!a.classification && a.epi.tgt) {  // PMML Target of a regression SVM (epilogue.h order)
@@ -98,7 +119,7 @@ __device__ __forceinline__ float svm_kernel_fn(const SvmArgs& a, float dot, floa
   }
 }
 
-template <int FMAX>
+template <int FMAX, bool CLASSES = false>
 __global__ __launch_bounds__(TB) void svm_kernel(SvmArgs a) {
   const int row = blockIdx.x * TB + threadIdx.x;
   if (row >= a.n_rows) return;
@@ -130,7 +151,7 @@ __global__ __launch_bounds__(TB) void svm_kernel(SvmArgs a) {
 #pragma unroll
     for (int m = 0; m < MMAX; ++m) acc[m] = fmaf(cj[m], k, acc[m]);
   }
-  svm_finish(a, row, acc, !bad && !miss);
+  svm_finish<CLASSES>(a, row, acc, !bad && !miss);
 }
 
 
@@ -147,7 +168,7 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 // NM: machines evaluated per support vector (1: binary / regression; MMAX: any, the padded
 // machines' coefficients are zero) — unconditional FMAs on a vector LDS read, no per-machine branch
-template <int FMAX, int KT, int NM>
+template <int FMAX, int KT, int NM, bool CLASSES = false>
 __global__ __launch_bounds__(TB) void svm_mfma_kernel(SvmArgs a, int n_svp) {
   constexpr int SVS = FMAX + 1;  // padded support-vector row: the 32 rows of an A fragment hit 32 banks
   extern __shared__ __align__(16) uint32_t smem[];
@@ -222,13 +243,13 @@ __global__ __launch_bounds__(TB) void svm_mfma_kernel(SvmArgs a, int n_svp) {
     for (int m = 0; m < MMAX; ++m) tot[m] = a.intercept[m] + (acc[h][m] + __shfl_xor(acc[h][m], 32));
     const int rl = rb + 32 * h;
     const int row = row0 + rl;
-    if (half == h && row < a.n_rows) svm_finish(a, row, tot, bad[rl] == 0 && !miss[h]);
+    if (half == h && row < a.n_rows) svm_finish<CLASSES>(a, row, tot, bad[rl] == 0 && !miss[h]);
   }
 }
 
-template <int FMAX, int KT>
+template <int FMAX, int KT, bool CLASSES>
 int launch_svm_mfma_k(hipStream_t stream, const SvmArgs& a, int n_svp, dim3 grid, size_t lds) {
-  auto k = a.n_machines == 1 ? svm_mfma_kernel<FMAX, KT, 1> : svm_mfma_kernel<FMAX, KT, MMAX>;
+  auto k = a.n_machines == 1 ? svm_mfma_kernel<FMAX, KT, 1, CLASSES> : svm_mfma_kernel<FMAX, KT, MMAX, CLASSES>;
   if (lds > 65536 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
           hipSuccess)
@@ -237,18 +258,41 @@ int launch_svm_mfma_k(hipStream_t stream, const SvmArgs& a, int n_svp, dim3 grid
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 
-template <int FMAX>
+template <int FMAX, bool CLASSES>
 int launch_svm_mfma(hipStream_t stream, const SvmArgs& a, int n_svp, dim3 grid, size_t lds) {
   switch (a.kernel) {
-    case K_POLY: return launch_svm_mfma_k<FMAX, K_POLY>(stream, a, n_svp, grid, lds);
-    case K_RBF: return launch_svm_mfma_k<FMAX, K_RBF>(stream, a, n_svp, grid, lds);
-    case K_SIGMOID: return launch_svm_mfma_k<FMAX, K_SIGMOID>(stream, a, n_svp, grid, lds);
-    default: return launch_svm_mfma_k<FMAX, K_LINEAR>(stream, a, n_svp, grid, lds);
+    case K_POLY: return launch_svm_mfma_k<FMAX, K_POLY, CLASSES>(stream, a, n_svp, grid, lds);
+    case K_RBF: return launch_svm_mfma_k<FMAX, K_RBF, CLASSES>(stream, a, n_svp, grid, lds);
+    case K_SIGMOID: return launch_svm_mfma_k<FMAX, K_SIGMOID, CLASSES>(stream, a, n_svp, grid, lds);
+    default: return launch_svm_mfma_k<FMAX, K_LINEAR, CLASSES>(stream, a, n_svp, grid, lds);
   }
 }
 
+// The fused kernels for one CLASSES value: the matrix-core kernel where it applies, else the VALU one.
+template <bool CLASSES>
+int launch_svm(hipStream_t stream, const SvmArgs& a, int fmax, int n_svp, dim3 grid) {
+  const size_t lds = (size_t)a.n_feat * TB * 4 + TB * 4 + (size_t)n_svp * (fmax + 1 + MMAX + 1) * 4;
+  if (n_svp >= 32 && (n_svp & 31) == 0 && a.n_feat <= 64 && lds <= 160 * 1024 && a.kernel >= 0 && a.kernel <= 3) {
+    switch (fmax) {
+      case 8: return launch_svm_mfma<8, CLASSES>(stream, a, n_svp, grid, lds);
+      case 16: return launch_svm_mfma<16, CLASSES>(stream, a, n_svp, grid, lds);
+      case 32: return launch_svm_mfma<32, CLASSES>(stream, a, n_svp, grid, lds);
+      case 64: return launch_svm_mfma<64, CLASSES>(stream, a, n_svp, grid, lds);
+      default: return -6;
+    }
+  }
+  switch (fmax) {
+    case 8: hipLaunchKernelGGL((svm_kernel<8, CLASSES>), grid, dim3(TB), 0, stream, a); break;
+    case 16: hipLaunchKernelGGL((svm_kernel<16, CLASSES>), grid, dim3(TB), 0, stream, a); break;
+    case 32: hipLaunchKernelGGL((svm_kernel<32, CLASSES>), grid, dim3(TB), 0, stream, a); break;
+    case 64: hipLaunchKernelGGL((svm_kernel<64, CLASSES>), grid, dim3(TB), 0, stream, a); break;
+    default: return -6;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
 // ------------------------------------------------------------------------------------------
-// Wide SVM kernel: any number of machines (one-against-one over many classes), up to 64 classes,
+// Wide SVM kernel: any number of machines (one-against-one over many classes), up to 256 classes,
 // up to 128 vector fields, any number of support vectors — the chained two-GEMM form of the
 // decision function fused in one pass, both GEMMs on the exact-fp32 matrix cores:
 //   G^T = S . X^T      (32 support vectors x 32 rows per MFMA tile, K = fields)
@@ -263,6 +307,10 @@ int launch_svm_mfma(hipStream_t stream, const SvmArgs& a, int n_svp, dim3 grid, 
 // contiguous 16-byte loads: svA [tile][lane][FMAX/2], coefA [tile][mtile][lane][16], svnP
 // [tile][half][16]. Machines run in groups of MT tiles (acc registers); a model with more
 // machines loops over groups, recomputing G per group. Votes go to packed u16 LDS counters.
+// Class outputs (CLASSES, picked when SvmArgs::probs is set): the lane that picks a row's winner
+// leaves the row's vote total (-1: no prediction) in TB more LDS words; after one more barrier all
+// threads stream the workgroup's contiguous [rows x n_classes] slice of probs from the counters,
+// consecutive lanes to consecutive addresses, 16-byte stores between a scalar head and tail.
 struct SvmWideArgs {
   SvmArgs s;              // rows, preparation, intercept / thr / tgt / alt ([n_groups*MT*32]), outputs
   const float* svA;       // [n_tiles][64][FMAX/2]
@@ -273,11 +321,11 @@ struct SvmWideArgs {
 
 constexpr int WTB = 512;  // wide kernel: 8 waves x 32 rows (one MFMA N tile per wave) = TB rows
 
-template <int FMAX, int MT>
+template <int FMAX, int MT, bool CLASSES = false>
 __global__ __launch_bounds__(WTB) void svm_wide_kernel(SvmWideArgs w) {
   const SvmArgs& a = w.s;
   constexpr int Q = FMAX / 2;
-  extern __shared__ __align__(16) uint32_t votes[];  // [TB][CW] packed u16 class counters
+  extern __shared__ __align__(16) uint32_t votes[];  // [TB][CW] packed u16 class counters (CLASSES: + [TB] totals)
   const int CW = (a.n_classes + 1) >> 1;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int rl = (tid >> 6) * 32 + l31;  // this lane's row within the tile (both halves share it)
@@ -381,39 +429,78 @@ __global__ __launch_bounds__(WTB) void svm_wide_kernel(SvmWideArgs w) {
     }
   }
   __syncthreads();
-  if (half != 0 || row >= a.n_rows) return;
-  float sc;
-  if (a.classification) {
-    int best = 0;
-    uint32_t bv = votes[rl * CW] & 0xFFFFu;
-    for (int c = 1; c < a.n_classes; ++c) {
-      const uint32_t v = (votes[rl * CW + (c >> 1)] >> (16 * (c & 1))) & 0xFFFFu;
-      if (v > bv) { bv = v; best = c; }  // ties: the first category
-    }
-    sc = a.epi.table[best];
-  } else {
-    sc = reg;
+  if constexpr (!CLASSES) {
+    if (half != 0 || row >= a.n_rows) return;
   }
-  bool ok = !bad && (sc == sc);
-  if (!a.classification && a.epi.tgt) {  // PMML Target of a regression SVM (epilogue.h order)
-    sc = apply_target(a.epi, sc);
-    if (!ok && (a.epi.tgt & TGT_DEFAULT)) {
-      sc = a.epi.dflt;
-      ok = true;
+  if (!CLASSES || (half == 0 && row < a.n_rows)) {  // CLASSES: every thread reaches the barrier below
+    float sc;
+    [[maybe_unused]] uint32_t total = 0u;  // CLASSES: the votes cast on this row
+    if (a.classification) {
+      int best = 0;
+      uint32_t bv = votes[rl * CW] & 0xFFFFu;
+      total = bv;
+      for (int c = 1; c < a.n_classes; ++c) {
+        const uint32_t v = (votes[rl * CW + (c >> 1)] >> (16 * (c & 1))) & 0xFFFFu;
+        if constexpr (CLASSES) total += v;
+        if (v > bv) { bv = v; best = c; }  // ties: the first category
+      }
+      if constexpr (CLASSES) sc = a.epi.table ? a.epi.table[best] : (float)best;
+      else sc = a.epi.table[best];
+    } else {
+      sc = reg;
     }
+    bool ok = !bad && (sc == sc);
+    if (!a.classification && a.epi.tgt) {  // PMML Target of a regression SVM (epilogue.h order)
+      sc = apply_target(a.epi, sc);
+      if (!ok && (a.epi.tgt & TGT_DEFAULT)) {
+        sc = a.epi.dflt;
+        ok = true;
+      }
+    }
+    const float so = ok ? sc : __builtin_nanf("");
+    a.score[row] = so;
+    a.valid[row] = ok ? 1 : 0;
+    if (a.epi.score2) {
+      a.epi.score2[row] = so;
+      a.epi.valid2[row] = ok ? 1 : 0;
+    }
+    if constexpr (CLASSES) votes[TB * CW + rl] = ok ? total : 0xFFFFFFFFu;  // at most 65535 machines vote
   }
-  const float so = ok ? sc : __builtin_nanf("");
-  a.score[row] = so;
-  a.valid[row] = ok ? 1 : 0;
-  if (a.epi.score2) {
-    a.epi.score2[row] = so;
-    a.epi.valid2[row] = ok ? 1 : 0;
+  if constexpr (CLASSES) {
+    __syncthreads();  // the rows' totals
+    // the workgroup's rows are one contiguous [rows here x C] slice of probs
+    const int C = a.n_classes;
+    const int row0 = blockIdx.x * TB;
+    const int n_el = min(TB, a.n_rows - row0) * C;
+    float* base = a.probs + (size_t)row0 * C;
+    const uint32_t* rtot = votes + TB * CW;
+    auto share = [&](int r, int c) -> float {
+      const uint32_t t = rtot[r];
+      const uint32_t v = (votes[r * CW + (c >> 1)] >> (16 * (c & 1))) & 0xFFFFu;
+      return t == 0xFFFFFFFFu ? __builtin_nanf("") : (float)v / (float)t;  // 0/0: no machine voted
+    };
+    const int head = min(n_el, (int)((4u - (uint32_t)((reinterpret_cast<uintptr_t>(base) >> 2) & 3u)) & 3u));
+    const int n_vec = (n_el - head) >> 2;
+    const int tail0 = head + 4 * n_vec;
+    if (tid < head) base[tid] = share(tid / C, tid % C);
+    for (int v = tid; v < n_vec; v += WTB) {
+      const int e = head + 4 * v;
+      int r = e / C, c = e - r * C;
+      float q[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        q[i] = share(r, c);
+        if (++c == C) { c = 0; ++r; }
+      }
+      *reinterpret_cast<float4*>(base + e) = make_float4(q[0], q[1], q[2], q[3]);
+    }
+    if (tid < n_el - tail0) base[tail0 + tid] = share((tail0 + tid) / C, (tail0 + tid) % C);
   }
 }
 
-template <int FMAX, int MT>
+template <int FMAX, int MT, bool CLASSES>
 int launch_svm_wide_t(hipStream_t stream, const SvmWideArgs& w, dim3 grid, size_t lds) {
-  auto k = svm_wide_kernel<FMAX, MT>;
+  auto k = svm_wide_kernel<FMAX, MT, CLASSES>;
   if (lds > 65536 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
           hipSuccess)
@@ -422,12 +509,23 @@ int launch_svm_wide_t(hipStream_t stream, const SvmWideArgs& w, dim3 grid, size_
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 
-template <int FMAX>
+template <int FMAX, bool CLASSES>
 int launch_svm_wide_f(hipStream_t stream, const SvmWideArgs& w, int mt, dim3 grid, size_t lds) {
   switch (mt) {
-    case 1: return launch_svm_wide_t<FMAX, 1>(stream, w, grid, lds);
-    case 2: return launch_svm_wide_t<FMAX, 2>(stream, w, grid, lds);
-    case 4: return launch_svm_wide_t<FMAX, 4>(stream, w, grid, lds);
+    case 1: return launch_svm_wide_t<FMAX, 1, CLASSES>(stream, w, grid, lds);
+    case 2: return launch_svm_wide_t<FMAX, 2, CLASSES>(stream, w, grid, lds);
+    case 4: return launch_svm_wide_t<FMAX, 4, CLASSES>(stream, w, grid, lds);
+    default: return -6;
+  }
+}
+
+template <bool CLASSES>
+int launch_svm_wide(hipStream_t stream, const SvmWideArgs& w, int fmax, int mt, dim3 grid, size_t lds) {
+  switch (fmax) {
+    case 16: return launch_svm_wide_f<16, CLASSES>(stream, w, mt, grid, lds);
+    case 32: return launch_svm_wide_f<32, CLASSES>(stream, w, mt, grid, lds);
+    case 64: return launch_svm_wide_f<64, CLASSES>(stream, w, mt, grid, lds);
+    case 128: return launch_svm_wide_f<128, CLASSES>(stream, w, mt, grid, lds);
     default: return -6;
   }
 }
@@ -440,32 +538,19 @@ PMML_API int pmml_svm_launch(hipStream_t stream, const SvmArgs* args, int fmax, 
   const SvmArgs a = *args;
   if (a.n_rows <= 0) return 0;
   if (a.n_machines > MMAX || a.n_classes > 16) return -4;
+  const bool classes = a.probs != nullptr;  // class outputs: vote shares, the index mode
+  if (classes && (!a.classification || a.n_classes < 1)) return -4;
+  if (a.classification && !classes && !a.epi.table) return -4;  // the index mode needs probs
   dim3 grid((a.n_rows + TB - 1) / TB);
-  const size_t lds = (size_t)a.n_feat * TB * 4 + TB * 4 + (size_t)n_svp * (fmax + 1 + MMAX + 1) * 4;
-  if (n_svp >= 32 && (n_svp & 31) == 0 && a.n_feat <= 64 && lds <= 160 * 1024 && a.kernel >= 0 && a.kernel <= 3) {
-    switch (fmax) {
-      case 8: return launch_svm_mfma<8>(stream, a, n_svp, grid, lds);
-      case 16: return launch_svm_mfma<16>(stream, a, n_svp, grid, lds);
-      case 32: return launch_svm_mfma<32>(stream, a, n_svp, grid, lds);
-      case 64: return launch_svm_mfma<64>(stream, a, n_svp, grid, lds);
-      default: return -6;
-    }
-  }
-  switch (fmax) {
-    case 8: hipLaunchKernelGGL(svm_kernel<8>, grid, dim3(TB), 0, stream, a); break;
-    case 16: hipLaunchKernelGGL(svm_kernel<16>, grid, dim3(TB), 0, stream, a); break;
-    case 32: hipLaunchKernelGGL(svm_kernel<32>, grid, dim3(TB), 0, stream, a); break;
-    case 64: hipLaunchKernelGGL(svm_kernel<64>, grid, dim3(TB), 0, stream, a); break;
-    default: return -6;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -7;
+  return classes ? launch_svm<true>(stream, a, fmax, n_svp, grid) : launch_svm<false>(stream, a, fmax, n_svp, grid);
 }
 
 PMML_API int pmml_svm_wide_args_size() { return (int)sizeof(SvmWideArgs); }
 
 // fmax in {16, 32, 64, 128} (vector fields padded), mt in {1, 2, 4} (machine tiles per group);
 // intercept / thr / tgt / alt hold n_groups * mt * 32 entries; n_classes <= 256 (votes: TB x 128
-// packed u16 counters = 128 KiB of LDS at most), at most 65535 machines per classifier.
+// packed u16 counters = 128 KiB of LDS at most, plus TB words of vote totals with probs: 129 KiB),
+// at most 65535 machines per classifier.
 PMML_API int pmml_svm_wide_launch(hipStream_t stream, const SvmWideArgs* args, int fmax, int mt) {
   const SvmWideArgs w = *args;
   const SvmArgs& a = w.s;
@@ -475,13 +560,11 @@ PMML_API int pmml_svm_wide_launch(hipStream_t stream, const SvmWideArgs* args, i
   if (w.n_tiles < 1 || w.n_groups < 1 || w.n_mtiles != w.n_groups * mt || a.n_machines > w.n_mtiles * 32) return -4;
   if (!a.classification && a.n_machines != 1) return -4;
   if (a.kernel < 0 || a.kernel > 3) return -4;
+  const bool classes = a.probs != nullptr;  // class outputs: vote shares, the index mode
+  if (classes && (!a.classification || a.n_classes < 1)) return -4;
+  if (a.classification && !classes && !a.epi.table) return -4;  // the index mode needs probs
   dim3 grid((a.n_rows + TB - 1) / TB);
   const size_t lds = (size_t)TB * ((a.n_classes + 1) / 2 > 0 ? (a.n_classes + 1) / 2 : 1) * 4;
-  switch (fmax) {
-    case 16: return launch_svm_wide_f<16>(stream, w, mt, grid, lds);
-    case 32: return launch_svm_wide_f<32>(stream, w, mt, grid, lds);
-    case 64: return launch_svm_wide_f<64>(stream, w, mt, grid, lds);
-    case 128: return launch_svm_wide_f<128>(stream, w, mt, grid, lds);
-    default: return -6;
-  }
+  return classes ? launch_svm_wide<true>(stream, w, fmax, mt, grid, lds + TB * 4)
+                 : launch_svm_wide<false>(stream, w, fmax, mt, grid, lds);
 }

@@ -260,6 +260,7 @@ class StreamingScorer:
         self.reason_codes = False  # ScoringConfig.reason_codes: passed to output_plan only
         self.entity_ranks = False  # ScoringConfig.entity_ranks: likewise
         self.knn_classes = False  # ScoringConfig.knn_classes: likewise
+        self.svm_classes = False  # ScoringConfig.svm_classes: likewise
         self._row_state = None  # score_row's persistent buffers
         self._row_lock = threading.Lock()  # ...shared by every caller of score_row
         from ..ops import _lib
@@ -471,7 +472,7 @@ class StreamingScorer:
         try:
             return compiled.output_plan(self.device, top_k=top_k, reason_codes=self.reason_codes,
                                         entity_ranks=self.entity_ranks, knn_classes=self.knn_classes,
-                                        **self.lowering_opts)
+                                        svm_classes=self.svm_classes, **self.lowering_opts)
         except NotLowerable as e:
             if self.fallback == "error":
                 raise
@@ -848,6 +849,7 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
     scorer.reason_codes = bool(cfg.reason_codes)
     scorer.entity_ranks = bool(cfg.entity_ranks)
     scorer.knn_classes = bool(cfg.knn_classes)
+    scorer.svm_classes = bool(cfg.svm_classes)
     return scorer
 
 

@@ -542,6 +542,20 @@ class WideMlpPlan(MlpPlan):
             t.record_stream(st)
 
 
+def _svm_probs(plan, X, probs, C: int) -> Optional[int]:
+    """Address of the ``[rows, classes]`` vote-share matrix an SVM plan's ``launch(probs=)`` fills (None:
+    no class outputs), checked before the launcher: contiguous fp32, one column per class, a classifier."""
+    if probs is None:
+        if plan.classification and plan.table is None:
+            raise ValueError("SVM index mode (table = None) needs probs")
+        return None
+    if not plan.classification:
+        raise ValueError("a regression SVM has no class vote shares (probs)")
+    if tuple(probs.shape) != (X.shape[0], C) or not probs.is_contiguous() or probs.dtype != X.dtype:
+        raise ValueError(f"probs must be a contiguous fp32 [{X.shape[0]}, {C}] matrix")
+    return probs.data_ptr()
+
+
 class SvmPlan(DevicePlan):
     """SupportVectorMachineModel on the fused kernel-evaluation + vote kernel (fp32)."""
 
@@ -641,6 +655,7 @@ class SvmPlan(DevicePlan):
         a.epi = _epilogue(mode=EPI_AFFINE, table=self.table, tgt=self.target_stage)
         a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
         a.score, a.valid, a.decision = _addr(score), _addr(valid), ptr(decision)
+        a.probs = _svm_probs(self, X, probs, self.n_classes)
         check(self.lib.pmml_svm_launch(stream_handle(stream), ctypes.byref(a), self.fmax,
                                        getattr(self, "n_svp", 0)), "svm kernel")
 
@@ -773,6 +788,7 @@ class SvmWidePlan(DevicePlan):
         a.epi = _epilogue(mode=EPI_AFFINE, table=self.table, tgt=self.target_stage)
         a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
         a.score, a.valid, a.decision = _addr(score), _addr(valid), ptr(decision)
+        a.probs = _svm_probs(self, X, probs, self.n_classes)
         w.svA, w.coefA, w.svnP = ptr(self.svA), ptr(self.coefA), ptr(self.svnP)
         w.n_tiles, w.n_mtiles, w.n_groups = self.n_tiles, self.n_groups * self.mt, self.n_groups
         check(self.lib.pmml_svm_wide_launch(stream_handle(stream), ctypes.byref(w), self.fmax, self.mt),
@@ -871,6 +887,7 @@ class SvmGemmPlan(DevicePlan):
             ctx = torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device))
         else:  # lowering dry run: the same tensor program on the host (CPU tests)
             ctx = contextlib.nullcontext()
+        _svm_probs(self, X, probs, int(self.vote_t.shape[1]) if self.classification else 0)
         with ctx:
             n = X.shape[0]
             for lo in range(0, n, self.ROW_CHUNK):
@@ -883,8 +900,13 @@ class SvmGemmPlan(DevicePlan):
                     if self.max_wins:
                         first = ~first
                     votes = first.float() @ self.vote_t + (~first).float() @ self.vote_a
-                    s = self.table[votes.argmax(dim=1)]  # ties -> first category, as np.argmax
+                    best = votes.argmax(dim=1)  # ties -> first category, as np.argmax
+                    # index mode (table cleared by an output plan): the score is the class index
+                    s = self.table[best] if self.table is not None else best.to(votes.dtype)
                     ok = ok & ~torch.isnan(s)
+                    if probs is not None:  # vote shares; 0/0 = NaN where no machine voted, NaN on invalid rows
+                        shares = votes / votes.sum(dim=1, keepdim=True)
+                        probs[lo:hi].copy_(torch.where(ok[:, None], shares, torch.full_like(shares, float("nan"))))
                 else:
                     s = D[:, 0]
                 s = torch.where(ok, s, torch.full_like(s, float("nan")))

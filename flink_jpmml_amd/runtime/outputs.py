@@ -37,6 +37,14 @@ instance's index): its ``probability`` columns are tables over the instances hol
 class field. Entity fields of the same document still go to the entity kernel (``entity_ranks=True``)
 or are refused by name.
 
+With ``svm_classes=True`` the class outputs of an SVM classifier are columns as well. The inner
+``SvmPlan`` / ``SvmWidePlan`` / ``SvmGemmPlan`` runs in index mode (``table = None``): the class-output
+instantiations of ``ops/csrc/svm.hip`` (the tensor program of ``SvmGemmPlan``) write the winning class
+index and the ``[rows, C]`` vote shares (``votes_c / Σ votes``; NaN in a row without a prediction and
+in a valid row on which no machine voted), and the ordinary column ops read them. More than 256
+classes are refused naming the first class field. Without the switch every class output of an SVM is
+refused by name.
+
 Known difference from the host path: a row that fails the MiningField preparation has NaN in every
 column on the host; on the device such a row is a row without a prediction, so a constant column
 (the probability of an undeclared class) and an expression that maps missing values keep their value.
@@ -48,7 +56,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from ..models.base import ModelEvaluator
+from ..models.base import ModelEvaluator, class_probabilities
 from ..ops import outputs as K
 from .plans import DevicePlan, NotLowerable, build_field_prep, compile_plan
 
@@ -87,10 +95,10 @@ class OutputPlan(DevicePlan):
     supports_direct = False
 
     def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, entity_ranks: bool = False,
-                 knn_classes: bool = False, **opts):
+                 knn_classes: bool = False, svm_classes: bool = False, **opts):
         super().__init__(compiled, device)
         from ..models.scorecard import ScorecardEvaluator
-        from .nn_plans import GemmMlpPlan, MlpPlan
+        from .nn_plans import GemmMlpPlan, MlpPlan, SvmGemmPlan, SvmPlan, SvmWidePlan
         from .plans import ClusterPlan, KnnPlan, LinearPlan, TreePlan
         from .segmented import SegmentedPlan, _index_outputs, probs_width
 
@@ -138,6 +146,21 @@ class OutputPlan(DevicePlan):
                 labels = list(base.labels)
                 C = len(labels)
                 self._knn_index = True
+        # class outputs of an SVM classifier: the vote kernels' index mode (table = None) and their shares
+        self._svm_index = False
+        if bool(svm_classes) and isinstance(base, (SvmPlan, SvmWidePlan, SvmGemmPlan)) \
+                and probe.kind == "classification":
+            if len(ev.categories) > K.MAX_CLASSES:  # only reachable on SvmGemmPlan
+                asked = [of for of in compiled.model.output
+                         if of.feature in ("predictedValue", "predictedDisplayValue", "probability")]
+                if asked:
+                    raise NotLowerable(f"output {asked[0].name!r}: {len(ev.categories)} classes > {K.MAX_CLASSES}")
+                if top_k:
+                    raise NotLowerable(f"top_k: {len(ev.categories)} classes > {K.MAX_CLASSES}")
+            else:
+                labels = list(ev.categories)
+                C = len(labels)
+                self._svm_index = True
         if isinstance(base, ClusterPlan):
             labels = list(ev.entity_ids)
         elif isinstance(base, (LinearPlan, TreePlan)):
@@ -199,7 +222,8 @@ class OutputPlan(DevicePlan):
         exprs = []
         reason_fields = []  # (Output field, its column of the matrix): written by the reason kernel
         entity_fields = []  # likewise, written by the entity kernel
-        need_probs = self.top_k > 0 or self._knn_index  # the vote kernel's index mode always writes its shares
+        # the vote kernels' index mode always writes its shares
+        need_probs = self.top_k > 0 or self._knn_index or self._svm_index
         need_aff = False
         custom = type(ev)._output_column is not ModelEvaluator._output_column
 
@@ -245,7 +269,7 @@ class OutputPlan(DevicePlan):
                 else:
                     col = (K.OP_NAN, 0, 0)
             elif feat == "probability":
-                if probe.probs is None or probe.categories is None:
+                if class_probabilities(probe) is None or probe.categories is None:
                     raise no(of, "the model has no probabilities")
                 if self._knn_one:
                     # the nearest instance casts the only vote: 1 for its class, 0 for every other
@@ -464,9 +488,9 @@ class OutputPlan(DevicePlan):
             v = np.where(valid, to_plan[np.where(valid, v, len(res.categories)).astype(np.int64)], np.nan)
             if self.C:
                 src = [list(res.categories).index(x) for x in self.labels]
-                probs = np.asarray(res.probs)[:, src]
+                probs = np.asarray(class_probabilities(res))[:, src]
         elif self.C:
-            probs = np.asarray(res.probs)
+            probs = np.asarray(class_probabilities(res))
         aff = np.asarray(res.affinity, dtype=np.float32) if self._affinity else None
         return (np.where(valid, v, np.nan).astype(np.float32), valid.astype(np.uint8),
                 None if probs is None else probs.astype(np.float32), aff)
@@ -576,9 +600,10 @@ def host_batch_outputs(compiled, X: np.ndarray, replace_nan: Optional[float] = N
     if res is not None and res.categories is not None:
         cats = list(res.categories)
     if top_k:
-        if res is None or res.probs is None:
+        probs = class_probabilities(res) if res is not None else None
+        if probs is None:
             raise NotLowerable("top_k: the model has no class probabilities")
-        ti, tp = oracle_top_k(res.probs, np.asarray(res.valid, dtype=bool) & ok, top_k)
+        ti, tp = oracle_top_k(probs, np.asarray(res.valid, dtype=bool) & ok, top_k)
     return s, v, BatchOutputs(names, matrix, compiled.schema, cats, ti, tp)
 
 
