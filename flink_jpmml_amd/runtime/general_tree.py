@@ -267,15 +267,16 @@ def pack_general(trees: List[GeneralTree], weights: List[float], P: int, schema)
 def emulate_general(packed: dict, X: np.ndarray, P: int, n_trees: int) -> np.ndarray:
     """numpy twin of the kernel walk (per row, per tree) -> ``[rows, P]`` accumulators, NaN for
     rows with a null tree (CPU tests)."""
-    nodes, children, preds, pool = packed["nodes"], packed["children"], packed["preds"], packed["pool"]
+    nodes, children, pool = packed["nodes"], packed["children"], packed["pool"]
     Xf = np.asarray(X, dtype=np.float32)
     out = np.zeros((len(Xf), P), dtype=np.float32)
-    T = preds[:, 3].copy().view(np.float32)
+    T = packed["preds"][:, 3].copy().view(np.float32)
+    preds = packed["preds"].tolist()  # plain ints: the interpreter below runs per row and instruction
 
     def ev(pc: int, x) -> int:
         st: List[int] = []
         while True:
-            op, f, a, cnt = (int(v) for v in preds[pc])
+            op, f, a, cnt = preds[pc]
             neg, op = (op >> 8) & 1, op & 0xFF
             if op == P_END:
                 return st[-1]
