@@ -319,7 +319,8 @@ class PmmlModel(Pipeline):
 
     def predict_batch_outputs(self, X: Any, replace_nan: Optional[float] = None, device: Any = None,
                               top_k: int = 0, reason_codes: bool = False, entity_ranks: bool = False,
-                              knn_classes: bool = False, svm_classes: bool = False, **opts):
+                              knn_classes: bool = False, svm_classes: bool = False,
+                              association_rules: bool = False, **opts):
         """:meth:`predict_batch` plus the model's ``<Output>`` fields: ``(scores, valid,
         BatchOutputs)`` for a ``[rows, active_fields]`` matrix. ``device=None`` runs the float64
         host oracle (numpy results), else the HIP output plan on that device (torch tensors).
@@ -331,7 +332,10 @@ class PmmlModel(Pipeline):
         clustering or k-NN model: ``entityId`` / ``clusterId`` / affinity of rank 1 … 32, the affinity
         of a named cluster, the neighbours' ids and distances. ``knn_classes`` scores the class outputs
         of a k-NN classifier on the device: the predicted label, the vote shares as ``probability``
-        and ``top_k``. ``svm_classes`` does the same for an SVM classifier (the machines' votes)."""
+        and ``top_k``. ``svm_classes`` does the same for an SVM classifier (the machines' votes).
+        ``association_rules`` ranks the matching rules of an AssociationModel on the device: its
+        ``ruleValue`` / ``entityId`` fields (rank 1 … 8) hold the rule's measure or the encoding of its
+        text; the scores are empty, as such a model has no target."""
         from .batch import BatchOutputs
 
         compiled = self.evaluator.model
@@ -341,7 +345,8 @@ class PmmlModel(Pipeline):
             return host_batch_outputs(compiled, np.asarray(X.detach().cpu().numpy() if hasattr(X, "detach") else X),
                                       replace_nan, None, top_k)
         plan = compiled.output_plan(device, top_k=top_k, reason_codes=reason_codes, entity_ranks=entity_ranks,
-                                    knn_classes=knn_classes, svm_classes=svm_classes, **opts)
+                                    knn_classes=knn_classes, svm_classes=svm_classes,
+                                    association_rules=association_rules, **opts)
         s, v, wide = plan.score_outputs(X, replace_nan=replace_nan)
         return s, v, BatchOutputs.from_wide(plan.names, wide, plan.top_k, compiled.schema, plan.categories)
 

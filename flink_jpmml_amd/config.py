@@ -77,6 +77,12 @@ class ScoringConfig:
     ``probability`` and ``top_k``. Off: such a field does not lower, and the Output fields of that
     model follow ``fallback``. Other models ignore it."""
 
+    association_rules: bool = False
+    """Rank the ``ruleValue`` / ``entityId`` Output fields of an AssociationModel (rank 1 … 8) on the
+    device when a batch is scored with ``outputs=True`` (``FJA_ASSOCIATION_RULES=1``). Off: the
+    Output fields of such a model are computed on the host, row by row. A document the rule kernel
+    cannot take follows ``fallback``. Other models ignore it."""
+
     host_threads: int = 0
     """Worker threads of the native host tree walk (``fallback="host"`` models, CPU-only ranks,
     direct CPU ``predict_batch``); 0 = ``FJA_HOST_THREADS`` or 1. Results do not depend on it."""
@@ -180,7 +186,9 @@ class ScoringConfig:
                   reason_codes=get("REASON_CODES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
                   entity_ranks=get("ENTITY_RANKS", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
                   knn_classes=get("KNN_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
-                  svm_classes=get("SVM_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")))
+                  svm_classes=get("SVM_CLASSES", lambda v: v.strip().lower() in ("1", "true", "yes", "on")),
+                  association_rules=get("ASSOCIATION_RULES",
+                                        lambda v: v.strip().lower() in ("1", "true", "yes", "on")))
         kw = {k: v for k, v in kw.items() if v is not None}
         kw.update({k: v for k, v in overrides.items() if v is not None})
         return ScoringConfig(**kw)

@@ -16,8 +16,12 @@ the PMML 4.x association-rule semantics:
   (1-based) is reported as its ``ruleFeature``: antecedent / consequent (the item value, or
   ``{a,b}`` for several items), ``rule`` (``{a}->{b}``), ``ruleId``, or one of the rule's measures.
 
-No device kernel: set matching over a handful of rules per basket is host work (SURVEY §2.8 lists
-no association op); the device path scores such models with the NullScorer (no target)."""
+This module is the specification of the device path. A bound model scores with the NullScorer (no
+target); its ``ruleValue`` / ``entityId`` fields are computed here, one Python loop per row, field and
+rule, unless ``association_rules=True`` (``ScoringConfig.association_rules``) sends them to
+``ops/csrc/rules.hip``: ``runtime/rules.py`` packs the items into per-row bit sets, presorts the rules
+per ``(algorithm, rankBasis, rankOrder)`` with the key of ``_ranked`` and stores what ``_rule_value``
+answers in per-field tables, so the kernel reports the same values bit for bit (docs/PARITY.md)."""
 
 from __future__ import annotations
 

@@ -299,7 +299,19 @@ class EntityArgs(ctypes.Structure):
                 ("Fp", c_int), ("p", c_float), ("pad", c_int)]
 
 
+class RuleArgs(ctypes.Structure):
+    """rules.hip RuleArgs: the packed association rules and the raw rows -> their ranked rules."""
+    _fields_ = [("X", c_void_p), ("prep", c_void_p), ("fields", c_void_p), ("imap", c_void_p), ("nvals", c_void_p),
+                ("pairs", c_void_p), ("scan", c_void_p), ("groups", c_void_p), ("cols", c_void_p),
+                ("tables", c_void_p), ("out", c_void_p),
+                ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("ldo", c_int), ("n_items", c_int),
+                ("n_rules", c_int), ("n_group", c_int), ("n_col", c_int), ("k", c_int), ("rows", c_int),
+                ("n_tables", c_int), ("n_pair", c_int), ("n_map", c_int), ("n_vals", c_int), ("pad0", c_int),
+                ("pad1", c_int)]
+
+
 _ABI = {
+    "pmml_rules_args_size": RuleArgs,
     "pmml_entities_args_size": EntityArgs,
     "pmml_reasons_args_size": ReasonArgs,
     "pmml_outputs_args_size": OutputArgs,
@@ -456,6 +468,10 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_entities_launch.restype = c_int
         lib.pmml_entities_lds_bytes.argtypes = [c_int, c_int, c_int]
         lib.pmml_entities_lds_bytes.restype = ctypes.c_longlong
+        lib.pmml_rules_launch.argtypes = [c_void_p, ctypes.POINTER(RuleArgs)]
+        lib.pmml_rules_launch.restype = c_int
+        lib.pmml_rules_lds_bytes.argtypes = [c_int, c_int, c_int]
+        lib.pmml_rules_lds_bytes.restype = ctypes.c_longlong
         _lib = lib
         return lib
 

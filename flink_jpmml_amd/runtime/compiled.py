@@ -121,23 +121,25 @@ class CompiledPmml:
     # ------------------------------------------------------------------ device
     def output_plan(self, device: Any = "cuda", top_k: int = 0, reason_codes: bool = False,
                     entity_ranks: bool = False, knn_classes: bool = False, svm_classes: bool = False,
-                    **opts):
+                    association_rules: bool = False, **opts):
         """The :class:`~flink_jpmml_amd.runtime.outputs.OutputPlan` of this model, lowered once per
-        (device, top_k, reason_codes, entity_ranks, knn_classes, svm_classes, options) and cached like :meth:`plan`.
+        (device, top_k, reason_codes, entity_ranks, knn_classes, svm_classes, association_rules, options) and
+        cached like :meth:`plan`.
         ``reason_codes`` ranks a Scorecard's ``reasonCode`` fields on the device, ``entity_ranks`` the
         ranked-entity fields of a clustering or k-NN model, ``knn_classes`` scores the class outputs
-        (label, vote shares, top-k) of a k-NN classifier, ``svm_classes`` those of an SVM classifier; other
+        (label, vote shares, top-k) of a k-NN classifier, ``svm_classes`` those of an SVM classifier,
+        ``association_rules`` ranks the ``ruleValue`` / ``entityId`` fields of an AssociationModel; other
         models ignore them."""
         from .outputs import OutputPlan
 
         key = f"outputs|{device}|{int(top_k)}|{bool(reason_codes)}|{bool(entity_ranks)}|{bool(knn_classes)}|" \
-              f"{bool(svm_classes)}|{sorted(opts.items())}"
+              f"{bool(svm_classes)}|{bool(association_rules)}|{sorted(opts.items())}"
         with self._lock:
             p = self._plans.get(key)
             if p is None:
                 p = OutputPlan(self, device, top_k=top_k, reason_codes=bool(reason_codes),
                                entity_ranks=bool(entity_ranks), knn_classes=bool(knn_classes),
-                               svm_classes=bool(svm_classes), **opts)
+                               svm_classes=bool(svm_classes), association_rules=bool(association_rules), **opts)
                 self._plans[key] = p
             return p
 

@@ -774,18 +774,40 @@ class HostScorer:
 
 class NullScorer:
     """A model without a named target field: the reference extracts nothing and every record is
-    ``EmptyScore`` (`S/api/PmmlModel.scala:167-174`)."""
+    ``EmptyScore`` (`S/api/PmmlModel.scala:167-174`). ``rule_plan``: the output plan of an
+    AssociationModel under ``ScoringConfig.association_rules`` (:func:`make_scorer` lowers it); with
+    it the Output fields of a batch come from the device, without it from the host oracle."""
 
     kind = "null"
     direct = False
 
-    def __init__(self, n_features: int, compiled=None):
+    def __init__(self, n_features: int, compiled=None, rule_plan=None):
         self.F = n_features
         self.compiled = compiled
+        self.rule_plan = rule_plan
+        self.device = rule_plan.device if rule_plan is not None else None
+
+    def _submit_rules(self, batch: RecordBatch, replace_nan: Optional[float]) -> PredictionBatch:
+        """The batch through the rule plan: one launch, one copy of the output matrix back."""
+        from ..api.batch import BatchOutputs
+
+        plan = self.rule_plan
+        if isinstance(batch, SparseRecordBatch) and self.F <= CSR_MAX_WIDTH:
+            _, _, wide = plan.score_csr_outputs(batch, replace_nan)
+        else:
+            _, _, wide = plan.score_outputs(batch.X, replace_nan, absent=batch.absent)
+        n = len(batch)
+        outs = BatchOutputs.from_wide(plan.names, wide.cpu().numpy(), 0, plan.compiled.schema, None)
+        METRICS.inc("scoring.rows_device", n)
+        METRICS.inc("scoring.batches_device")
+        return PredictionBatch(n, np.full(n, np.nan, dtype=np.float32), np.zeros(n, dtype=bool),
+                               row_ok=batch.size_ok(), outputs=outs)
 
     def submit_batch(self, batch: RecordBatch, replace_nan: Optional[float] = None,
                      keep_device: bool = False, outputs: bool = False, top_k: int = 0) -> PredictionBatch:
         METRICS.inc("scoring.empty_score.no_target", len(batch))
+        if outputs and self.rule_plan is not None and not top_k and len(batch) and batch.n_features == self.F:
+            return self._submit_rules(batch, replace_nan)
         if outputs and self.compiled is not None and len(batch) and batch.n_features == self.F:
             from .outputs import host_batch_outputs  # every score is empty, the Output fields are not
 
@@ -806,11 +828,37 @@ def _set_host_threads(n: int) -> None:
         fp.set_walk_threads(int(n))
 
 
+def _rule_plan(compiled, device, cfg):
+    """The output plan of an AssociationModel under ``cfg.association_rules`` on ``device``, or None:
+    switch off, no device, another model, or a document the rule kernel cannot take and a fallback
+    policy that allows the host path (``error`` fails the load instead)."""
+    from ..models.association import AssociationEvaluator
+    from .plans import NotLowerable
+
+    if device is None or not cfg.association_rules or not isinstance(compiled.evaluator, AssociationEvaluator):
+        return None
+    try:
+        with prange("model.lower"):
+            return compiled.output_plan(device, association_rules=True, **cfg.lowering_opts())
+    except NotLowerable as e:
+        if cfg.fallback == "error":
+            from ..api.exceptions import ModelLoadingException
+
+            raise ModelLoadingException(f"Output fields of model {compiled.model_name!r} are not lowerable to "
+                                        f"{device}: {e}", e) from e
+        METRICS.inc("scoring.host_fallback_outputs")
+        if cfg.fallback == "warn":
+            logger.warning("Output fields of model %r cannot run on %s (%s): computing them on the "
+                           "host oracle (set fallback='error' to refuse)", compiled.model_name, device, e)
+        return None
+
+
 def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline] = None, plan=None,
                 lower_error: Optional[str] = None):
     """The scorer for ``compiled`` on ``device`` under ``config``'s fallback policy.
 
-    * no target field → :class:`NullScorer`;
+    * no target field → :class:`NullScorer` (for an AssociationModel under ``config.association_rules``
+      on a device: with the output plan that ranks its rules, lowered here under the same policy);
     * ``device is None`` → :class:`HostScorer`;
     * otherwise the device plan; a model the device path cannot lower goes to the host oracle with
       a WARNING + ``scoring.host_fallback_models`` (``fallback="warn"``), only counted
@@ -820,7 +868,7 @@ def make_scorer(compiled, device, config=None, pipeline: Optional[DevicePipeline
 
     cfg = config or ScoringConfig()
     if not compiled.target_fields:
-        return NullScorer(compiled.n_features, compiled)
+        return NullScorer(compiled.n_features, compiled, _rule_plan(compiled, device, cfg))
     if cfg.host_threads:
         _set_host_threads(cfg.host_threads)
     if device is None:

@@ -45,6 +45,14 @@ in a valid row on which no machine voted), and the ordinary column ops read them
 classes are refused naming the first class field. Without the switch every class output of an SVM is
 refused by name.
 
+With ``association_rules=True`` an AssociationModel has an output plan at all: it has no target field,
+so there is no inner scoring plan (without the switch ``compile_plan`` refuses it). ``launch`` fills
+``score`` with NaN and ``valid`` with 0, and ``ops/csrc/rules.hip`` ranks the matching rules of every
+row from the raw rows and the document's ``FieldPrep`` (``runtime/rules.py``), writing the
+``ruleValue`` / ``entityId`` columns straight into the output matrix. Fields the base oracle answers
+with NaN are ``OP_NAN`` columns; an expression beside them and ``top_k`` are refused by name. A row
+that fails the preparation holds NaN in every rule column, as on the host.
+
 Known difference from the host path: a row that fails the MiningField preparation has NaN in every
 column on the host; on the device such a row is a row without a prediction, so a constant column
 (the probability of an undeclared class) and an expression that maps missing values keep their value.
@@ -95,8 +103,9 @@ class OutputPlan(DevicePlan):
     supports_direct = False
 
     def __init__(self, compiled, device, top_k: int = 0, reason_codes: bool = False, entity_ranks: bool = False,
-                 knn_classes: bool = False, svm_classes: bool = False, **opts):
+                 knn_classes: bool = False, svm_classes: bool = False, association_rules: bool = False, **opts):
         super().__init__(compiled, device)
+        from ..models.association import AssociationEvaluator
         from ..models.scorecard import ScorecardEvaluator
         from .nn_plans import GemmMlpPlan, MlpPlan, SvmGemmPlan, SvmPlan, SvmWidePlan
         from .plans import ClusterPlan, KnnPlan, LinearPlan, TreePlan
@@ -107,6 +116,11 @@ class OutputPlan(DevicePlan):
             raise ValueError(f"top_k must be in [0, {K.MAX_TOP_K}], got {top_k}")
         self.top_k = top_k
         ev = compiled.evaluator
+        self.rules = None  # the packed association rules (ops.rules.RuleTables) when the rule kernel runs
+        self._association = False
+        if bool(association_rules) and isinstance(ev, AssociationEvaluator):
+            self._lower_association(compiled, ev)  # no target, no inner scoring plan: the rule kernel alone
+            return
         # reasonCode fields of a scorecard rank on the device (ops/csrc/reasons.hip); off: refused by name
         self._rank_reasons = bool(reason_codes) and isinstance(ev, ScorecardEvaluator)
         self.reasons = None  # the packed scorecard (ops.reasons.ReasonTables) when a reason kernel runs
@@ -377,6 +391,93 @@ class OutputPlan(DevicePlan):
             self.expr_inputs = [compiled.active_fields.index(f) for f in inputs]
         self._dst = None
 
+    def _lower_association(self, compiled, ev) -> None:
+        """An AssociationModel under ``association_rules=True``: its ``ruleValue`` / ``entityId``
+        fields go to the rule kernel (``runtime/rules.py``), the fields the base oracle answers with
+        NaN stay ``OP_NAN`` columns of the column program, every other field is refused by name."""
+        from .rules import RULE_FEATURES, lower_rules
+
+        if self.top_k:
+            raise NotLowerable("top_k: an AssociationModel has no classes")
+        self._association = True
+        self.result_kind = "association"
+        self.inner = self.reasons = self.entities = self.expr = self._reason_prep = None
+        self.labels = self.label_table = self.categories = self.C = self._no_index = None
+        self._affinity = self._rank_reasons = self._rank_entities = False
+        self._knn_one = self._knn_index = self._svm_index = False
+        self.names = [of.name for of in compiled.model.output]
+        self.width = len(self.names)
+        self.kernel_names: List[str] = []
+        rule_fields = []
+        for j, of in enumerate(compiled.model.output):
+            feat = of.feature
+            if feat in RULE_FEATURES:
+                rule_fields.append((of, j))
+            elif feat in ("transformedValue", "decision") and of.expression is not None:
+                raise NotLowerable(f"output {of.name!r}: an expression beside the rule columns of an "
+                                   f"AssociationModel is host-only")
+            elif feat in ("predictedValue", "predictedDisplayValue", "transformedValue") or feat in _NAN_FEATURES:
+                self.kernel_names.append(of.name)  # no target, no result: NaN as the base oracle answers
+            else:
+                raise NotLowerable(f"output {of.name!r}: feature {feat!r} is not available for an AssociationModel")
+        self.n_named = len(self.kernel_names)
+        self.n_col = max(1, self.n_named)
+        if self.n_col > K.MAX_COLUMNS:
+            raise NotLowerable(f"outputs: {self.n_col} columns > {K.MAX_COLUMNS}")
+        self.prog_np = np.array([(K.OP_NAN, 0, 0, 0)] * self.n_col, dtype=np.int32).reshape(-1, 4)
+        self.tables_np = np.array([0.0], dtype=np.float32)
+        self.prog, self.tables = self._t(self.prog_np), self._t(self.tables_np)
+        self.kernel_dst = [self.names.index(n) for n in self.kernel_names]
+        self.direct_out = False
+        self._dst = None
+        if rule_fields:
+            self.rules = lower_rules(ev, compiled, rule_fields, self.width)
+
+    def _launch_association(self, X, score, valid, st, outputs, score2, valid2) -> None:
+        """No inner plan: every score is empty, the ``OP_NAN`` columns come from the column program
+        over that empty result, the rule columns from ``rules.hip`` over the raw rows."""
+        import torch
+
+        from ..ops.rules import rules_launch
+
+        n = int(X.shape[0])
+        with torch.cuda.stream(st):
+            raw_s = torch.full((n,), float("nan"), dtype=torch.float32, device=self.device)
+            raw_v = torch.zeros(n, dtype=torch.uint8, device=self.device)
+            if outputs is None:
+                outputs = self.alloc_matrix(n)
+            if self.kernel_dst:
+                out = torch.empty((n, self.n_col), dtype=torch.float32, device=self.device)
+                K.outputs_launch(raw_s, raw_v, out, self.prog, self.tables, stream=st)
+                if self._dst is None:
+                    self._dst = torch.tensor(self.kernel_dst, dtype=torch.int64, device=self.device)
+                outputs.index_copy_(1, self._dst, out)
+                out.record_stream(st)
+            if self.rules is not None:
+                rules_launch(X, outputs, self.rules, prep=self.prep, stream=st)
+            for dst, src in ((score, raw_s), (valid, raw_v), (score2, raw_s), (valid2, raw_v)):
+                if dst is not None:
+                    dst.copy_(src)
+            raw_s.record_stream(st)
+            raw_v.record_stream(st)
+
+    def _launch_association_host(self, X, score, valid, outputs, score2, valid2) -> None:
+        """Lowering dry run of :meth:`_launch_association` through the kernels' numpy twins."""
+        from ..ops.rules import rules_numpy
+
+        Xn = np.asarray(X.numpy() if hasattr(X, "numpy") else X, dtype=np.float32)
+        n = len(Xn)
+        out, s, v = K.outputs_numpy(np.full(n, np.nan, dtype=np.float32), np.zeros(n, dtype=np.uint8), self.prog_np,
+                                    self.tables_np)
+        full = np.full((n, self.width), np.nan, dtype=np.float32)
+        if self.kernel_dst:
+            full[:, self.kernel_dst] = out[:, : len(self.kernel_dst)]
+        if self.rules is not None:
+            rules_numpy(Xn, full, self.rules, prep=self.prep.numpy() if self.prep is not None else None)
+        for dst, src in ((score, s), (valid, v), (outputs, full), (score2, s), (valid2, v)):
+            if dst is not None:
+                (dst.numpy() if hasattr(dst, "numpy") else dst)[...] = src
+
     def _lower_reasons(self, compiled, ev, reason_fields) -> None:
         """The reason kernel reads the matrix the scorecard's general tree kernel reads: the raw
         rows with this plan's FieldPrep, or the tile the inner derive pass writes."""
@@ -424,6 +525,9 @@ class OutputPlan(DevicePlan):
         from .segmented import run_expression_program
 
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if self._association:
+            self._launch_association(X, score, valid, st, outputs, score2, valid2)
+            return
         with torch.cuda.stream(st):
             raw_s = torch.empty(n, dtype=torch.float32, device=self.device)
             raw_v = torch.empty(n, dtype=torch.uint8, device=self.device)
@@ -500,6 +604,9 @@ class OutputPlan(DevicePlan):
         ``derive.emulate``."""
         from .derive import emulate
 
+        if self._association:
+            self._launch_association_host(X, score, valid, outputs, score2, valid2)
+            return
         Xn = X.numpy() if hasattr(X, "numpy") else np.asarray(X)
         Xn = np.asarray(Xn, dtype=np.float32)
         raw_s, raw_v, probs, aff = self.raw_from_oracle(Xn)
