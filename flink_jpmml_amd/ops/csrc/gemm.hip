@@ -484,7 +484,8 @@ __device__ __forceinline__ void decode_row(const GemmArgs& a, int row, const flo
     if (p > best || (p == best && u < best_u)) { best = p; best_u = u; }
     if (a.probs) a.probs[(size_t)row * a.n_out + u] = p;
   }
-  bool ok = !bad && best == best && best_u < a.n_out;
+  // simplemax over outputs that sum to 0: z / 0 is no probability (the row has no prediction)
+  bool ok = !bad && best == best && best_u < a.n_out && !(a.final_norm == 2 && sum == 0.f);
   float sc = ok ? (a.epi.has_table ? a.epi.table[best_u] : (float)best_u) : __builtin_nanf("");
   ok = ok && (sc == sc);
   a.score[row] = ok ? sc : __builtin_nanf("");
@@ -689,7 +690,8 @@ __global__ __launch_bounds__(256) void nn_decode_wide_kernel(GemmArgs a, const f
     if (p > best || (p == best && u < best_u)) { best = p; best_u = u; }
     if (a.probs) a.probs[(size_t)row * a.n_out + u] = p;
   }
-  bool ok = !bad && best == best && best_u < a.n_out;
+  // simplemax over outputs that sum to 0: z / 0 is no probability (the row has no prediction)
+  bool ok = !bad && best == best && best_u < a.n_out && !(a.final_norm == 2 && sum == 0.f);
   float sc = ok ? (a.epi.has_table ? a.epi.table[best_u] : (float)best_u) : __builtin_nanf("");
   ok = ok && (sc == sc);
   a.score[row] = ok ? sc : __builtin_nanf("");

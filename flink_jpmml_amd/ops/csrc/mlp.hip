@@ -425,7 +425,9 @@ __global__ __launch_bounds__(64 * Cfg<BF16>::WAVES, 1) void mlp_kernel(MlpArgs a
     const int ou = __shfl_xor(best_u, 32);
     if (ob > best || (ob == best && ou < best_u)) { best = ob; best_u = ou; }
     if (h == 0 && in_range) {
-      bool ok = (rbad[0] | rbad[1]) == 0 && best == best && best_u < a.n_out;
+      // simplemax over outputs that sum to 0: z / 0 is no probability (the row has no prediction)
+      bool ok = (rbad[0] | rbad[1]) == 0 && best == best && best_u < a.n_out &&
+                !(a.final_norm == 2 && sum == 0.f);
       float sc = ok ? (a.epi.has_table ? a.epi.table[best_u] : (float)best_u) : __builtin_nanf("");
       ok = ok && (sc == sc);
       a.score[row] = ok ? sc : __builtin_nanf("");
@@ -767,7 +769,8 @@ __device__ __forceinline__ void repilogue(const MlpArgs& a, Out out, bool bad, i
     if (p > best || (p == best && u < best_u)) { best = p; best_u = u; }
     if (a.probs) a.probs[(size_t)row * a.n_out + u] = p;
   }
-  bool ok = !bad && best == best && best_u < a.n_out;
+  // simplemax over outputs that sum to 0: z / 0 is no probability (the row has no prediction)
+  bool ok = !bad && best == best && best_u < a.n_out && !(a.final_norm == 2 && sum == 0.f);
   float sc = ok ? (a.epi.has_table ? a.epi.table[best_u] : (float)best_u) : __builtin_nanf("");
   ok = ok && (sc == sc);
   a.score[row] = ok ? sc : __builtin_nanf("");

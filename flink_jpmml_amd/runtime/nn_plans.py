@@ -61,8 +61,17 @@ def mlp_panels(meta, precision: str) -> np.ndarray:
     return np.array(out, dtype=np.int32)
 
 
-def pack_mlp_weights(layers: List[Tuple[np.ndarray, np.ndarray]], precision: str):
-    """Pack ``[(W[in, out], b[out])]`` into MFMA A-fragments.
+def pad_bias(act: str) -> float:
+    """Bias of a hidden layer's padded units (all their weights are 0, and so are the next layer's
+    weights on them): their activation must be finite, or the next layer's ``0 * inf`` turns every
+    row into NaN. ``reciprocal`` is the one activation with a pole at 0; its padded units sit at 1."""
+    return 1.0 if act == "reciprocal" else 0.0
+
+
+def pack_mlp_weights(layers: List[Tuple[np.ndarray, np.ndarray]], precision: str,
+                     pad_biases: Optional[List[float]] = None):
+    """Pack ``[(W[in, out], b[out])]`` into MFMA A-fragments. ``pad_biases``: per layer, the bias of
+    the padded units (:func:`pad_bias`; default 0).
 
     Returns ``(weights (flat), biases (flat), meta rows [kp, mp, mreal, w_off, b_off])``."""
     frags: List[np.ndarray] = []
@@ -107,7 +116,7 @@ def pack_mlp_weights(layers: List[Tuple[np.ndarray, np.ndarray]], precision: str
                         kk = 32 * tp + (r & 3) + 8 * (r >> 2) + 4 * hh
                     out[t, s] = At[32 * t + m_idx, kk]
         frags.append(out.reshape(-1))
-        bb = np.zeros(mp)
+        bb = np.full(mp, pad_biases[L] if pad_biases is not None else 0.0)
         bb[:M] = b
         biases.append(bb)
         meta.append((kp, mp, M, w_off, b_off))
@@ -153,7 +162,8 @@ class MlpPlan(DevicePlan):
             raise NotLowerable(f"more than {KMAX} inputs (fused kernel)")
         if self.n_out > 32:
             raise NotLowerable("more than 32 output neurons (fused kernel)")
-        w, bias, meta = pack_mlp_weights([(W, b) for W, b, *_ in layers], precision)
+        w, bias, meta = pack_mlp_weights([(W, b) for W, b, *_ in layers], precision,
+                                         [pad_bias(act) for _, _, act, *_ in layers])
         pan = mlp_panels(meta, precision)
         self.panels = self._t(pan.reshape(-1))
         self.n_panels = int(len(pan))
@@ -333,6 +343,7 @@ class GemmMlpPlan(MlpPlan):
                     p = torch.softmax(h, dim=1)
                 elif self.final_norm == 2:
                     p = h / h.sum(dim=1, keepdim=True)
+                    ok = ok & (h.sum(dim=1) != 0)  # z / 0 is no probability
                 else:
                     p = h
                 lab = torch.argmax(torch.nan_to_num(p, nan=-float("inf")), dim=1)
@@ -408,7 +419,7 @@ class WideMlpPlan(MlpPlan):
             mp = _ceil(m, 32) if head else _ceil(m, 256)  # output layer: 32-unit groups
             Wt = np.zeros((mp, kp), dtype=np.float32)
             Wt[:m, :k] = np.asarray(W, np.float32).T
-            bias = np.zeros(mp, dtype=np.float32)
+            bias = np.full(mp, 0.0 if head else pad_bias(act), dtype=np.float32)
             bias[:m] = b
             wts.append(Wt.reshape(-1))
             bss.append(bias)

@@ -147,17 +147,24 @@ def int_network(n_in: int, hidden: Sequence[int], n_out: int, seed: int, taps: i
     return layers
 
 
-def nn_pmml(layers: Layers, classification: bool = False, normalization: Optional[str] = "softmax") -> str:
+def nn_pmml(layers: Layers, classification: bool = False, normalization: Optional[str] = "softmax",
+            activations: Optional[Sequence[str]] = None, thresholds: Optional[Sequence[Optional[float]]] = None,
+            net_threshold: Optional[float] = None, net_normalization: Optional[str] = None) -> str:
     """NeuralNetwork document of ``layers``: identity inputs (LinearNorm -1 -> -1, 1 -> 1), rectifier
     hidden layers, an identity output layer (``normalization`` for classification); only the
-    non-zero connections are written."""
+    non-zero connections are written. ``activations`` names every layer's ``activationFunction``
+    instead (the network's stays rectifier), ``thresholds`` a ``threshold`` per layer (None: not
+    written), ``net_threshold`` / ``net_normalization`` the NeuralNetwork element's own attributes
+    (a layer without one inherits them). Weights and biases may then be dyadic fractions."""
     n_in, n_out = layers[0][0].shape[0], layers[-1][0].shape[1]
     out = io.StringIO()
     _header(out, "exact-integer network " + "-".join(str(W.shape[1]) for W, _ in layers))
     cats = [str(c) for c in range(n_out)] if classification else None
     _data_dictionary(out, n_in, "y", "integer" if classification else "double", cats)
     fn = "classification" if classification else "regression"
-    out.write(f' <NeuralNetwork functionName="{fn}" activationFunction="rectifier">\n')
+    net = "" if net_threshold is None else f' threshold="{_num(net_threshold)}"'
+    net += f' normalizationMethod="{net_normalization}"' if net_normalization else ""
+    out.write(f' <NeuralNetwork functionName="{fn}" activationFunction="rectifier"{net}>\n')
     _mining_schema(out, n_in, "y", "  ")
     out.write('  <NeuralInputs>\n')
     for j in range(n_in):
@@ -167,9 +174,12 @@ def nn_pmml(layers: Layers, classification: bool = False, normalization: Optiona
     out.write('  </NeuralInputs>\n')
     prev = [f"i{j}" for j in range(n_in)]
     for li, (W, b) in enumerate(layers):
-        attrs = ""
+        attrs = "" if activations is None else f' activationFunction="{activations[li]}"'
+        if thresholds is not None and thresholds[li] is not None:
+            attrs += f' threshold="{_num(thresholds[li])}"'
         if li == len(layers) - 1:
-            attrs = ' activationFunction="identity"'
+            if activations is None:
+                attrs = ' activationFunction="identity"'
             if classification and normalization:
                 attrs += f' normalizationMethod="{normalization}"'
         out.write(f'  <NeuralLayer{attrs}>\n')
