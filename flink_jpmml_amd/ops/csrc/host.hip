@@ -14,9 +14,13 @@ PMML_API int pmml_memcpy_async(void* dst, const void* src, size_t bytes, int kin
 
 // Page-lock an existing host range (e.g. a memory-mapped file in the page cache) so copy engines
 // DMA straight from it: flags = hipHostRegister* (ReadOnly for PROT_READ mappings). Returns a
-// hipError_t.
+// hipError_t. Where the platform refuses (a guest without host-range registration), the caller reads
+// into pinned buffers instead, so the refusal must not stay behind as the runtime's last error:
+// the next launcher's hipGetLastError() would report it as a failed kernel launch.
 PMML_API int pmml_host_register(void* p, size_t bytes, unsigned flags) {
-  return (int)hipHostRegister(p, bytes, flags);
+  const hipError_t rc = hipHostRegister(p, bytes, flags);
+  if (rc != hipSuccess) (void)hipGetLastError();
+  return (int)rc;
 }
 
 PMML_API int pmml_host_unregister(void* p) { return (int)hipHostUnregister(p); }

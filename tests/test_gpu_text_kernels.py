@@ -69,6 +69,22 @@ def test_nine_missing_tokens_are_refused(gpu, lib):
     assert _run(lib, gpu, c, missing=tuple(f"m{i}" for i in range(8)))["rc"] == 0
 
 
+def test_refused_registration_leaves_no_error_for_the_next_launch(gpu, lib):
+    """A host range the runtime will not page-lock (here: an empty one) is reported by the return
+    code alone; the launcher that runs next (the reader's first, once it has fallen back to the
+    pinned ring) must not find the refusal as the runtime's last error."""
+    import torch
+
+    assert lib.pmml_host_register(None, 0, 0) != 0
+    text = b"1,2\n3,4\n5,6\n7,8\n"
+    buf = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(gpu)
+    counts = torch.zeros(2, dtype=torch.int32, device=gpu)  # one tile: its offset, then the total
+    rc = lib.pmml_text_rows_count(torch.cuda.current_stream(gpu).cuda_stream, buf.data_ptr(), len(text),
+                                  counts.data_ptr())
+    assert rc == 0
+    assert counts.cpu().tolist() == [0, len(T.twin_row_starts(text))] == [0, 4]
+
+
 # --------------------------------------------------------------------------- the reader
 
 
