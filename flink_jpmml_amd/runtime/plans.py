@@ -1607,8 +1607,9 @@ class TreePlan(DevicePlan):
         return False
 
     # -- PERFECT layout (narrow and wide kernels)
-    def _lower_perfect(self, compiled, opt, stage, rows, wide_ok: bool) -> bool:
+    def _lower_perfect(self, compiled, opt, stage, rows, wide_ok: bool, vote8_ok: bool = True) -> bool:
         spec, depth, F = self.spec, self.depth, compiled.n_features
+        self.blob_nan, self.chunk_trees_nan, self.feat_map, self.tree_w = None, 0, None, None
         self.variant = int(opt.variant == "wide" or (opt.variant == "auto" and not self.general and wide_ok))
         if self.variant == 1:
             if not wide_ok:
@@ -1624,7 +1625,7 @@ class TreePlan(DevicePlan):
             stride, fmap = TB, None
         leaf_bits = None
         if spec.mode == "class":
-            self.mode = self._vote_mode(spec, rows)
+            self.mode = self._vote_mode(spec, rows) if vote8_ok else 2
             if self.mode == 3:  # VOTE8: packed u8 counters, the leaf is the increment 1 << 8*class
                 leaf_bits = "vote8"
             elif spec.tree_w is not None and any(w != 1.0 for w in spec.tree_w):
@@ -1655,6 +1656,17 @@ class TreePlan(DevicePlan):
                 self.blob_nan = self._t(blob_nan.reshape(-1).view(np.int32))
             else:
                 self.variant &= ~(VAR_NAN_FAST | VAR_NAN_PLANES)
+        if self.mode == 3:
+            # the u8 counters hold what the kernel's grouping really gives a thread, on either blob.
+            # The chunk sizes depend on the record, and the record on the mode (class codes drop the
+            # leaf array), so the count is known only now: lower once more as MODE_CLASS. The second
+            # pass must not see the first one's work: everything this method assigns is either
+            # reset on entry (blob_nan, chunk_trees_nan, feat_map, tree_w) or assigned again on
+            # every pass (variant, mode, rows_wide, n_stage, rec_words, chunk_trees, blob); acc_init
+            # and the fp8 scale in epi_args belong to slot / sum ensembles, which never come here.
+            G = 1024 // self.rows_wide
+            if max(self.vote8_peak(self.n_trees, c, G) for c in (self.chunk_trees, self.chunk_trees_nan)) > 255:
+                return self._lower_perfect(compiled, opt, stage, rows, wide_ok, vote8_ok=False)
         self.blob = self._t(blob.reshape(-1).view(np.int32))
         return has_dr
 
@@ -1867,7 +1879,9 @@ class TreePlan(DevicePlan):
 
     def _vote_mode(self, spec, rows) -> int:
         """MODE_VOTE8 (packed u8 counters, one add per tree) when the vote is unweighted, <= 4
-        classes, no leaf lacks a class and no thread's counter can pass 255; else MODE_CLASS."""
+        classes, no leaf lacks a class and ``ceil(n_trees / G) <= 255``; else MODE_CLASS. That count
+        is what a thread walks when the chunks are multiples of G (``_chunk`` sees to it);
+        ``_lower_perfect`` checks the real count once the chunks are known (:meth:`vote8_peak`)."""
         G = 1024 // (rows or 256)
         unweighted = spec.tree_w is None or all(w == 1.0 for w in spec.tree_w)
         no_nan = all(not np.isnan(t.leaf_value[t.feature < 0]).any() for t in spec.trees)
@@ -1875,11 +1889,24 @@ class TreePlan(DevicePlan):
             return 3
         return 2
 
+    @staticmethod
+    def vote8_peak(n_trees: int, chunk: int, G: int) -> int:
+        """The most trees one thread of the wide kernel walks: group g takes trees ``k = g (mod G)``
+        *of every chunk* (csrc traverse_fast_g / traverse_chunk_g: ``mt = (nt - g + G - 1) / G``),
+        so a chunk that is no multiple of G gives its first groups one tree more, chunk after chunk.
+        It bounds a MODE_VOTE8 thread's packed u8 counters."""
+        if chunk < 1:
+            return 0
+        full, last = divmod(n_trees, chunk)
+        return max(full * ((chunk - g + G - 1) // G) + max(0, (last - g + G - 1) // G) for g in range(G))
+
     def _chunk(self, fit: int, wide: bool, cap: int, slot_cap: int = 0) -> int:
         """Trees per LDS chunk. Wide kernel: whole ILP batches per tree group (G groups x 8-wide
         walks) — every group gets the same count (no barrier imbalance) and no latency-bound short
         tail batches (measured: 64 > 79 > 57 trees at depth 6). MODE_SUM claims 8-tree batches
-        dynamically: whole batches, at most ``slot_cap`` trees (one LDS slot per batch)."""
+        dynamically: whole batches, at most ``slot_cap`` trees (one LDS slot per batch).
+        MODE_VOTE8: a multiple of G where one fits, so every group walks ``ceil(n_trees / G)``
+        trees at most (:meth:`vote8_peak`)."""
         c = int(max(1, min(self.n_trees, fit)))
         if slot_cap:
             c = min(c, slot_cap)
@@ -1887,7 +1914,10 @@ class TreePlan(DevicePlan):
         if wide and c < self.n_trees:
             q = DYN_B if slot_cap else (8 * G if c >= 16 * G else 2 * G)
             c = max(q, c // q * q) if c >= q else c
-        return min(c, cap) if cap > 0 else c
+        c = min(c, cap) if cap > 0 else c
+        if wide and self.mode == 3 and G <= c < self.n_trees:
+            c = c // G * G
+        return c
 
     @staticmethod
     def _general_spec(compiled) -> "EnsembleSpec":

@@ -15,6 +15,7 @@ import torch
 from flink_jpmml_amd.bench.synth import gbdt_pmml, random_forest_pmml, stream_matrix
 from flink_jpmml_amd.runtime.compiled import CompiledPmml
 from flink_jpmml_amd.runtime.plans import VAR_NAN_FAST, VAR_NAN_PLANES, TreePlan, lowering_dry_run
+from tests._wide_cases import emulate_wide, peak
 
 
 def _plan(txt, **kw):
@@ -23,85 +24,12 @@ def _plan(txt, **kw):
         return c, TreePlan(c, torch.device("cpu"), **kw)
 
 
-def emulate_wide(plan, X, use_nan_blob):
-    """Per-row result of the wide kernel; ``use_nan_blob`` picks the tile path (NaN blob + two
-    planes, as for a tile with missing values) — without it missing values take the per-node
-    default-right bits (traverse_chunk_g)."""
-    D, n_t, rec = plan.depth, plan.n_trees, plan.rec_words
-    NI, NL = (1 << D) - 1, 1 << D
-    PS = plan.rows_wide
-    G = 1024 // plan.rows_wide
-    stage = plan.feat_map.numpy() if plan.feat_map is not None else np.arange(plan.n_features)
-    Xs = X[:, stage].astype(np.float32)
-    Fs = Xs.shape[1]
-    blob = (plan.blob_nan if use_nan_blob else plan.blob).numpy().view(np.uint32).reshape(n_t, rec)
-    planes = np.concatenate([Xs, np.where(np.isnan(Xs), np.float32(np.inf), Xs)], axis=1) if use_nan_blob else Xs
-    chunk = plan.chunk_trees_nan if use_nan_blob else plan.chunk_trees
-    per_node = not use_nan_blob and not (plan.variant & VAR_NAN_FAST)
-    n = len(X)
-    rows = np.arange(n)
-    C = plan.C
-    acc = np.zeros((n, max(C, 1)), np.float64)
-    votes = np.zeros((G, n, 4), np.int64)
-    pz = np.zeros(n, bool)
-    slots = plan.slots.numpy() if plan.slots is not None else None
-    tree_w = plan.tree_w.numpy() if plan.tree_w is not None else np.ones(n_t, np.float32)
-    for t in range(n_t):
-        T = blob[t, 0:2 * NI:2].view(np.float32)
-        meta = blob[t, 1:2 * NI:2]
-        codes = plan.variant & 3 == 2  # VOTE8 class codes in the last-level metas (no leaf array)
-        leaves = None if codes else blob[t, 2 * NI:2 * NI + NL]
-        drw = blob[t, 2 * NI + (0 if codes else NL):2 * NI + (0 if codes else NL) + (NI + 31) // 32]
-        j = np.ones(n, np.int64)
-        miss = np.zeros(n, bool)
-        for lev in range(D):
-            off = meta[j - 1].astype(np.int64) & (0xFFFF if codes and lev == D - 1 else 0xFFFFFFFF)
-            assert (off % (PS * 4) == 0).all()
-            x = planes[rows, off // (PS * 4)]
-            right = x >= T[j - 1]
-            if per_node:
-                isn = np.isnan(x)
-                right |= isn & (((drw[(j - 1) >> 5] >> ((j - 1) & 31)) & 1) == 1)
-                miss |= isn
-            j = 2 * j + right
-        null_tree = (drw[NI >> 5] >> (NI & 31)) & 1
-        if codes:
-            pm = meta[(j >> 1) - 1]
-            lv = np.uint32(1) << (np.uint32(8) * ((pm >> np.where(j & 1, 24, 16).astype(np.uint32)) & 3))
-        else:
-            lv = leaves[j - NL]
-        poison = miss & (null_tree == 1)
-        if plan.mode == 0:
-            acc[:, 0] += np.where(poison, np.nan, lv.view(np.float32))
-        elif plan.mode == 1:
-            acc[~poison, slots[t]] += lv.view(np.float32)[~poison]
-        elif plan.mode == 2:
-            v = lv.view(np.float32)
-            pz |= poison | np.isnan(v)
-            ok = ~poison & ~np.isnan(v)
-            acc[rows[ok], v[ok].astype(int)] += tree_w[t]
-        else:
-            g = (t % chunk) % G
-            for k in range(4):
-                votes[g, ~poison, k] += (lv[~poison] >> (8 * k)) & 0xFF
-        pz |= poison
-    if plan.mode == 3:
-        assert votes.max() <= 255  # a thread's packed u8 counter never carries
-        acc = votes.sum(axis=0)[:, :C].astype(np.float64)
-    if plan.acc_init is not None:
-        acc += plan.acc_init.numpy()[None, :]
-    tab = np.array([float(x) for x in plan.labels]) if plan.labels is not None else None
-    e = plan.epi_args
-    if plan.mode == 0 and e["mode"] == 0:
-        return np.where(np.isnan(acc[:, 0]), np.nan, e["a"] * acc[:, 0] + e["b"])
-    if plan.mode == 0 and e["mode"] == 1:
-        p0 = 1.0 / (1.0 + np.exp(-(e["a"] * acc[:, 0] + e["b"])))
-        return np.where(np.isnan(acc[:, 0]), np.nan, tab[np.where(p0 >= 0.5, 0, 1)])
-    return np.where(pz, np.nan, tab[np.argmax(acc, axis=1)])  # argmax: ties -> lowest class
-
-
 def _check(c, plan, X, tol=0.0):
     ref, vref = c.score_matrix_oracle(X)
+    if plan.mode == 3:
+        # trees a thread walks as the kernel groups them ((t % chunk) % G, either blob's chunk size):
+        # its packed u8 counters hold no more
+        assert peak(plan) <= 255
     paths = [False] + ([True] if plan.blob_nan is not None else [])
     for use_nan in paths:
         # with a NaN blob, the main blob only ever sees tiles without missing values
