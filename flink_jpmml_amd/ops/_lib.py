@@ -235,6 +235,14 @@ class LinearArgs(ctypes.Structure):
                 ("listed", c_void_p)]
 
 
+class LinearWideArgs(ctypes.Structure):
+    """linear_wide.hip LinearWideArgs: W [Fp, Kp] and bias [Kp] zero padded, listed [F, Kp / 32] words."""
+    _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("K", c_int),
+                ("prep", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("Kp", c_int), ("Fp", c_int),
+                ("simplemax", c_int), ("pad", c_int), ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p),
+                ("probs", c_void_p), ("listed", c_void_p)]
+
+
 class MlpArgs(ctypes.Structure):
     _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("n_layers", c_int),
                 ("in_scale", c_void_p), ("in_shift", c_void_p), ("in_missing", c_void_p), ("in_index", c_void_p),
@@ -330,6 +338,7 @@ _ABI = {
     "pmml_gemm_args_size": GemmArgs,
     "pmml_nn_prep_args_size": NnPrepArgs,
     "pmml_linear_args_size": LinearArgs,
+    "pmml_linear_wide_args_size": LinearWideArgs,
     "pmml_mlp_args_size": MlpArgs,
     "pmml_svm_args_size": SvmArgs,
     "pmml_svm_wide_args_size": SvmWideArgs,
@@ -404,6 +413,8 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_knn_launch.argtypes = [c_void_p, ctypes.POINTER(KnnArgs), c_void_p, c_void_p, ctypes.c_int,
                                         ctypes.c_int]
         lib.pmml_linear_launch.argtypes = [c_void_p, ctypes.POINTER(LinearArgs)]
+        lib.pmml_linear_wide_launch.restype = c_int
+        lib.pmml_linear_wide_launch.argtypes = [c_void_p, ctypes.POINTER(LinearWideArgs)]
         if hasattr(lib, "pmml_mlp_launch"):
             lib.pmml_mlp_launch.argtypes = [c_void_p, ctypes.POINTER(MlpArgs), c_int]
         if hasattr(lib, "pmml_svm_launch"):

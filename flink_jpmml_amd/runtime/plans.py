@@ -338,7 +338,7 @@ class DevicePlan:
 
         from ..ops import _lib
 
-        cls = {c.__name__: c for c in (TreePlan, ClusterPlan, KnnPlan, LinearPlan)}.get(meta["__class__"])
+        cls = {c.__name__: c for c in (TreePlan, ClusterPlan, KnnPlan, LinearPlan, LinearWidePlan)}.get(meta["__class__"])
         if cls is None and meta["__class__"] == "DerivedPlan":
             from .derive import DerivedPlan as cls
         if cls is None and meta["__class__"] == "SegmentedPlan":
@@ -713,6 +713,11 @@ class KnnPlan(DevicePlan):
 # --------------------------------------------------------------------------- linear
 
 
+class LinearSizeLimit(NotLowerable):
+    """Dense regression tables beyond a linear kernel's table / field limits (nothing else is wrong
+    with the model: compile_plan moves on to the next wider kernel)."""
+
+
 class LinearPlan(DevicePlan):
     kind = "linear"
     _STATE = DevicePlan._STATE + ("W", "b", "K", "simplemax", "table", "epi_args", "listed")
@@ -729,8 +734,8 @@ class LinearPlan(DevicePlan):
             pass
         W, b = ev.dense_weights()
         if W.shape[1] > self.MAX_TABLES or compiled.n_features > self.MAX_FIELDS:
-            raise NotLowerable(f"linear kernel holds {self.MAX_TABLES} tables x {self.MAX_FIELDS} fields, got "
-                               f"{W.shape[1]} x {compiled.n_features}")
+            raise LinearSizeLimit(f"{self.kind} kernel holds {self.MAX_TABLES} tables x {self.MAX_FIELDS} fields, "
+                                  f"got {W.shape[1]} x {compiled.n_features}")
         Wf = np.zeros((compiled.n_features, W.shape[1]))
         for i, name in enumerate(ev.numeric_fields):
             if name not in compiled.active_fields:
@@ -741,17 +746,26 @@ class LinearPlan(DevicePlan):
             self.used[compiled.active_fields.index(name)] = True
         if not self.used.all():
             raise NotLowerable("unused active fields would wrongly invalidate rows with missing values")
-        self.W = self._t(Wf.astype(np.float32))
-        self.b = self._t(b.astype(np.float32))
         self.K = W.shape[1]
-        # bit k of listed[f]: table k lists predictor f. The oracle never multiplies a predictor a
-        # table does not list, so the dense 0 there must not meet an infinite input (0 * inf = NaN);
-        # None when every table lists every predictor
-        listed = np.zeros(compiled.n_features, dtype=np.int64)
+        # listed[f, k]: table k lists predictor f. The oracle never multiplies a predictor a table
+        # does not list, so the dense 0 there must not meet an infinite input (0 * inf = NaN)
+        listed = np.zeros((compiled.n_features, self.K), dtype=bool)
+        column = {name: f for f, name in enumerate(compiled.active_fields)}
         for k, t in enumerate(ev.rm.tables):
             for p in t.numeric:
-                listed[compiled.active_fields.index(p.name)] |= 1 << k
-        self.listed = None if (listed == (1 << self.K) - 1).all() else self._t(listed.astype(np.int32))
+                listed[column[p.name], k] = True
+        self._pack(Wf.astype(np.float32), b.astype(np.float32), listed)
+        self._select_epilogue(ev)
+
+    def _pack(self, Wf: np.ndarray, b: np.ndarray, listed: np.ndarray) -> None:
+        """The kernel's operands: W [F, K], b [K] and bit k of listed[f] (None when every table
+        lists every predictor)."""
+        self.W = self._t(Wf)
+        self.b = self._t(b)
+        bits = (listed.astype(np.int64) << np.arange(self.K, dtype=np.int64)[None, :]).sum(axis=1)
+        self.listed = None if listed.all() else self._t(bits.astype(np.int32))
+
+    def _select_epilogue(self, ev) -> None:
         norm = ev.rm.normalization_method
         self.simplemax = 0
         if ev.kind == "classification":
@@ -803,6 +817,46 @@ class LinearPlan(DevicePlan):
         a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
         a.listed = ptr(getattr(self, "listed", None))
         check(self.lib.pmml_linear_launch(stream_handle(stream), ctypes.byref(a)), "linear kernel")
+
+
+class LinearWidePlan(LinearPlan):
+    """Dense regression tables past LinearPlan's limits, on the matrix cores (csrc/linear_wide.hip):
+    the same tables, labels and epilogue, W and b zero padded to the kernel's 32 x 32 tiles."""
+
+    kind = "linear_wide"
+    _STATE = LinearPlan._STATE + ("Kp", "Fp")
+    MAX_TABLES, MAX_FIELDS = 256, 1024  # csrc/linear_wide.hip: KMAX, FMAX
+
+    def _pack(self, Wf: np.ndarray, b: np.ndarray, listed: np.ndarray) -> None:
+        """W [Fp, Kp] and b [Kp], zero padded to multiples of 32; listed [F, Kp / 32] words, bit
+        k % 32 of word k // 32: table k lists predictor f (None when every table lists every one)."""
+        F, K = Wf.shape
+        self.Kp, self.Fp = -(-K // 32) * 32, -(-F // 32) * 32
+        Wp = np.zeros((self.Fp, self.Kp), dtype=np.float32)
+        Wp[:F, :K] = Wf
+        bp = np.zeros(self.Kp, dtype=np.float32)
+        bp[:K] = b
+        self.W, self.b = self._t(Wp), self._t(bp)
+        bits = np.zeros((F, self.Kp), dtype=np.uint8)
+        bits[:, :K] = listed
+        words = np.packbits(bits, axis=1, bitorder="little").view("<u4")  # [F, Kp / 32]
+        self.listed = None if listed.all() else self._t(words.view(np.int32))
+
+    def launch(self, X, score, valid, stream=None, probs=None, score2=None, valid2=None) -> None:
+        import ctypes
+
+        from ..ops._lib import LinearWideArgs, check, ptr, stream_handle
+
+        a = LinearWideArgs()
+        a.X = ptr(X)
+        a.n_rows, a.n_feat, a.ldx, a.K = X.shape[0], X.shape[1], X.stride(0), self.K
+        a.prep, a.W, a.bias, a.simplemax = ptr(self.prep), ptr(self.W), ptr(self.b), self.simplemax
+        a.Kp, a.Fp = self.Kp, self.Fp
+        a.epi = _epilogue(table=self.table, write_probs=probs is not None, **self.epi_args)
+        a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
+        a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
+        a.listed = ptr(self.listed)
+        check(self.lib.pmml_linear_wide_launch(stream_handle(stream), ctypes.byref(a)), "wide linear kernel")
 
 
 # --------------------------------------------------------------------------- tree ensembles
@@ -2232,7 +2286,10 @@ def compile_plan(compiled, device, **opts) -> DevicePlan:
                 raise
             return _segmented_plan(compiled, device, e, dict(opts, precision=policy))
     if isinstance(ev, RegressionEvaluator):
-        return LinearPlan(compiled, device)
+        try:
+            return LinearPlan(compiled, device)
+        except LinearSizeLimit:  # past 16 tables x 128 fields: the MFMA kernel (256 x 1024)
+            return LinearWidePlan(compiled, device)
     from ..models.regression import GeneralRegressionEvaluator
 
     if isinstance(ev, GeneralRegressionEvaluator):
