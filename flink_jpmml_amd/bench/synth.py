@@ -327,6 +327,62 @@ def mlp_pmml(n_features: int = 64, hidden: Tuple[int, ...] = (256, 256), n_out: 
     return out.getvalue()
 
 
+def rbf_pmml(n_features: int = 64, hidden: int = 256, n_out: int = 1, seed: int = 0, classification: bool = False,
+             normalization: Optional[str] = None, altitude: float = 1.0, per_neuron: bool = True) -> str:
+    """Radial-basis-function NeuralNetwork: ``hidden`` radialBasis units (centres ~ N(0, 1), widths
+    ``sqrt(n_features) * U(0.8, 1.2)``, hidden ``normalization`` none / softmax / simplemax) and an
+    identity output layer (softmax for a classifier). ``per_neuron``: every third unit carries its own
+    width and altitude, the others take the layer's width and the network's altitude; off: the
+    network's values alone."""
+    rng = np.random.default_rng(seed)
+    out = io.StringIO()
+    _header(out, f"synthetic RBF network {n_features}-{hidden}-{n_out}")
+    cats = [str(c) for c in range(n_out)] if classification else None
+    _data_dictionary(out, n_features, "y", "integer" if classification else "double", cats)
+    fn = "classification" if classification else "regression"
+    base = np.sqrt(n_features)
+    out.write(f' <NeuralNetwork functionName="{fn}" activationFunction="radialBasis" width="{base:.7g}" '
+              f'altitude="{altitude:.9g}">\n')
+    _mining_schema(out, n_features, "y", "  ")
+    out.write('  <NeuralInputs>\n')
+    for j in range(n_features):
+        mu, sd = rng.standard_normal() * 0.1, 1.0 + 0.1 * rng.random()
+        out.write(f'   <NeuralInput id="i{j}"><DerivedField optype="continuous" dataType="double">'
+                  f'<NormContinuous field="f{j}"><LinearNorm orig="{mu - sd:.6f}" norm="-1"/>'
+                  f'<LinearNorm orig="{mu + sd:.6f}" norm="1"/></NormContinuous></DerivedField></NeuralInput>\n')
+    out.write('  </NeuralInputs>\n')
+    centres = rng.standard_normal((hidden, n_features))
+    widths = base * rng.uniform(0.8, 1.2, hidden)
+    alts = altitude * (1.0 + 0.1 * rng.uniform(-1.0, 1.0, hidden) / n_features)
+    attrs = f' width="{base * 1.1:.7g}"' if per_neuron else ""
+    if normalization:
+        attrs += f' normalizationMethod="{normalization}"'
+    out.write(f'  <NeuralLayer{attrs}>\n')
+    for k in range(hidden):
+        own = f' width="{widths[k]:.7g}" altitude="{alts[k]:.9g}"' if per_neuron and k % 3 == 0 else ""
+        out.write(f'   <Neuron id="h{k}"{own}>')
+        out.write("".join(f'<Con from="i{j}" weight="{centres[k, j]:.7g}"/>' for j in range(n_features)))
+        out.write('</Neuron>\n')
+    out.write('  </NeuralLayer>\n')
+    # normalised activations sum to 1 over the layer: the weights grow with it, so outputs stay O(1)
+    scale = np.sqrt(hidden) if normalization else 4.0 / np.sqrt(hidden)
+    V = rng.standard_normal((n_out, hidden)) * scale
+    b = rng.standard_normal(n_out) * 0.05
+    out.write('  <NeuralLayer activationFunction="identity"'
+              + (' normalizationMethod="softmax"' if classification else ' normalizationMethod="none"') + '>\n')
+    for k in range(n_out):
+        out.write(f'   <Neuron id="o{k}" bias="{b[k]:.7g}">')
+        out.write("".join(f'<Con from="h{j}" weight="{V[k, j]:.7g}"/>' for j in range(hidden)))
+        out.write('</Neuron>\n')
+    out.write('  </NeuralLayer>\n  <NeuralOutputs>\n')
+    for k in range(n_out):
+        ex = f'<NormDiscrete field="y" value="{k}"/>' if classification else '<FieldRef field="y"/>'
+        out.write(f'   <NeuralOutput outputNeuron="o{k}"><DerivedField optype="continuous" dataType="double">'
+                  f'{ex}</DerivedField></NeuralOutput>\n')
+    out.write('  </NeuralOutputs>\n </NeuralNetwork>\n</PMML>\n')
+    return out.getvalue()
+
+
 def svm_pmml(n_features: int = 16, n_sv: int = 256, seed: int = 0, kernel: str = "radialBasis",
              classification: bool = True, gamma: float = 0.05, n_classes: int = 2) -> str:
     """libsvm / sklearn-style SVM PMML; ``n_classes > 2`` exports one-against-one machines (one per

@@ -116,6 +116,52 @@ class NeuralEvaluator(ModelEvaluator):
             prev_ids = [n.id for n in layer.neurons]
         return out
 
+    def rbf_layers(self) -> dict:
+        """Lower a radial-basis-function network — exactly two layers, ``radialBasis`` then a dense
+        layer — to ``centers [H, n_in]``, per-unit ``width`` / ``altitude`` (neuron, then layer, then
+        network value, as :meth:`forward` resolves them), ``fan_in``, the hidden ``normalization`` and
+        the dense ``output`` layer ``(W[H, out], b[out], activation, threshold, normalization)``.
+        Raises :class:`~flink_jpmml_amd.runtime.plans.NotLowerable` naming what it refuses."""
+        from ..runtime.plans import NotLowerable
+
+        layers = self.nn.layers
+        acts = [self._layer_params(layer)[0] for layer in layers]
+        if len(layers) > 2:
+            raise NotLowerable(f"radial-basis network with more than two layers ({len(layers)})")
+        if len(layers) != 2 or acts[0] != "radialBasis" or acts[1] == "radialBasis":
+            raise NotLowerable("a radialBasis layer must be the first of two layers, followed by a dense layer")
+        in_ids = [inp.id for inp in self.nn.inputs]
+        idx = {nid: i for i, nid in enumerate(in_ids)}
+        hidden = layers[0]
+        H = len(hidden.neurons)
+        centers = np.zeros((H, len(in_ids)))
+        width, altitude = np.zeros(H), np.zeros(H)
+        for j, neu in enumerate(hidden.neurons):
+            srcs = [s for s, _ in neu.connections]
+            if sorted(srcs) != sorted(in_ids):
+                raise NotLowerable(f"radialBasis unit {neu.id!r} is not connected to every input exactly once")
+            for src, w in neu.connections:
+                centers[j, idx[src]] = w
+            wd = neu.width if neu.width is not None else (hidden.width or self.nn.width)
+            alt = neu.altitude if neu.altitude is not None else (hidden.altitude or self.nn.altitude)
+            if wd is None or not wd > 0.0:
+                raise NotLowerable(f"radialBasis unit {neu.id!r}: width <= 0 (or none given)")
+            if alt is None or not alt > 0.0:
+                raise NotLowerable(f"radialBasis unit {neu.id!r}: altitude <= 0")
+            width[j], altitude[j] = wd, alt
+        act, thr, norm = self._layer_params(layers[1])
+        hid = {neu.id: j for j, neu in enumerate(hidden.neurons)}
+        W = np.zeros((H, len(layers[1].neurons)))
+        b = np.zeros(len(layers[1].neurons))
+        for k, neu in enumerate(layers[1].neurons):
+            b[k] = neu.bias
+            for src, w in neu.connections:
+                if src not in hid:
+                    raise NotLowerable("connection skips a layer (the output layer reads a network input)")
+                W[hid[src], k] += w
+        return dict(centers=centers, width=width, altitude=altitude, fan_in=len(in_ids),
+                    normalization=self._layer_params(hidden)[2], output=(W, b, act, thr, norm))
+
     def input_columns(self, cols: Columns) -> np.ndarray:
         mats = []
         for inp in self.nn.inputs:

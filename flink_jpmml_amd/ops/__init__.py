@@ -2,7 +2,8 @@
 
 Kernels (``csrc/``): ``tree.hip`` (perfect / pointer / wide tree-ensemble traversal, split
 reduce), ``cluster.hip`` (center-based clustering), ``linear.hip`` (regression tables + links),
-``mlp.hip`` (fused all-layer MFMA MLP, bf16 and fp32), ``svm.hip`` (kernel eval + votes),
+``mlp.hip`` (fused all-layer MFMA MLP, bf16 and fp32), ``rbf.hip`` (radial-basis-function
+networks: distances, activation and output layer as two chained MFMA products), ``svm.hip`` (kernel eval + votes),
 ``sparse.hip`` (CSR record batches expanded into the dense input tile; wrapper and numpy twin in
 ``sparse.py``), ``outputs.hip`` (Output fields and top-k classes; ``outputs.py``), ``reasons.hip``
 (ranked Scorecard reason codes; wrapper, packed tables and numpy twin in ``reasons.py``),

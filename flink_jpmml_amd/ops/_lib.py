@@ -253,6 +253,16 @@ class MlpArgs(ctypes.Structure):
                 ("reg_kernel", c_int), ("pad_", c_int)]
 
 
+class RbfArgs(ctypes.Structure):
+    """rbf.hip RbfArgs: a radial-basis-function network's packed panels and the rows to score."""
+    _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("n_in", c_int),
+                ("in_scale", c_void_p), ("in_shift", c_void_p), ("in_missing", c_void_p), ("in_index", c_void_p),
+                ("panels", c_void_p), ("out_bias", c_void_p), ("kp", c_int), ("n_tiles", c_int),
+                ("hidden_norm", c_int), ("out_act", c_int), ("out_thr", c_float), ("a_max", c_float),
+                ("final_norm", c_int), ("n_out", c_int), ("classification", c_int), ("contiguous", c_int),
+                ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p), ("probs", c_void_p)]
+
+
 class SvmArgs(ctypes.Structure):
     _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("n_sv", c_int),
                 ("prep", c_void_p), ("in_index", c_void_p), ("sv", c_void_p), ("sv_norm", c_void_p),
@@ -340,6 +350,7 @@ _ABI = {
     "pmml_linear_args_size": LinearArgs,
     "pmml_linear_wide_args_size": LinearWideArgs,
     "pmml_mlp_args_size": MlpArgs,
+    "pmml_rbf_args_size": RbfArgs,
     "pmml_svm_args_size": SvmArgs,
     "pmml_svm_wide_args_size": SvmWideArgs,
 }
@@ -417,6 +428,8 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_linear_wide_launch.argtypes = [c_void_p, ctypes.POINTER(LinearWideArgs)]
         if hasattr(lib, "pmml_mlp_launch"):
             lib.pmml_mlp_launch.argtypes = [c_void_p, ctypes.POINTER(MlpArgs), c_int]
+        lib.pmml_rbf_launch.restype = c_int
+        lib.pmml_rbf_launch.argtypes = [c_void_p, ctypes.POINTER(RbfArgs)]
         if hasattr(lib, "pmml_svm_launch"):
             lib.pmml_svm_launch.argtypes = [c_void_p, ctypes.POINTER(SvmArgs), c_int, c_int]
         if hasattr(lib, "pmml_svm_wide_launch"):

@@ -191,6 +191,16 @@ class MlpPlan(DevicePlan):
         lm = self.layer_meta.cpu().numpy()
         return [tuple(int(x) for x in row[:5]) for row in lm]
 
+    def _layers(self, ev):
+        """The network's layers as ``_io`` reads them: ``[(W, b, activation, threshold, normalization)]``."""
+        layers = ev.dense_layers()
+        for i, (W, b, act, thr, norm) in enumerate(layers):
+            if act not in ACT_CODES:
+                raise NotLowerable(f"activation {act!r}")
+            if norm not in (None, "none") and i != len(layers) - 1:
+                raise NotLowerable("hidden-layer normalisation is host-only")
+        return layers
+
     def _io(self, compiled, ev):
         """Inputs (NormContinuous affine maps, missing replacements, active-field index), the
         dense layers, output normalisation and the target decode. Returns ``(layers, index)``."""
@@ -209,12 +219,7 @@ class MlpPlan(DevicePlan):
             misses.append(miss)
             index.append(compiled.active_fields.index(field))
         self.n_in = len(index)
-        layers = ev.dense_layers()
-        for i, (W, b, act, thr, norm) in enumerate(layers):
-            if act not in ACT_CODES:
-                raise NotLowerable(f"activation {act!r}")
-            if norm not in (None, "none") and i != len(layers) - 1:
-                raise NotLowerable("hidden-layer normalisation is host-only")
+        layers = self._layers(ev)
         self.in_scale = self._t(np.array(scales, np.float32))
         self.in_shift = self._t(np.array(shifts, np.float32))
         self.in_missing = self._t(np.array(misses, np.float32))
@@ -276,6 +281,135 @@ class MlpPlan(DevicePlan):
         a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
         a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
         check(self.lib.pmml_mlp_launch(stream_handle(stream), ctypes.byref(a), self.bf16), "mlp kernel")
+
+
+RBF_KPS = (16, 32, 64, 128)  # padded input counts csrc/rbf.hip is instantiated for
+RBF_HMAX = 1024  # hidden units
+RBF_AMAX = 64.0  # softmax shifts by A_max = max altitude^fanIn: exp(-64) is still a normal fp32
+RBF_TAIL = 1024 + 128  # panel floats after the centre fragments (mirrors csrc/rbf.hip TAIL)
+_HIDDEN_NORMS = {None: 0, "none": 0, "softmax": 1, "simplemax": 2}
+
+
+def pack_rbf_panels(Wc: np.ndarray, c: np.ndarray, g: np.ndarray, V: np.ndarray, kp: int) -> np.ndarray:
+    """One panel per 32-unit hidden tile, ``[tiles, kp * 32 + RBF_TAIL]`` float32, in the order the
+    lanes of ``csrc/rbf.hip`` consume it. ``Wc [H, n_in]`` centres (centroid removed), ``c`` / ``g``
+    per-unit constants, ``V [n_out, H]`` output weights; float64 in, rounded once.
+
+    * centre fragments ``[q][lane][e]`` = ``Wc[32 t + (lane & 31), 8 q + 4 (lane >> 5) + e]``;
+    * output weights ``[r4][lane][e]`` = ``V[lane & 31, 32 t + unit(4 r4 + e, lane >> 5)]`` with
+      ``unit(r, h) = (r & 3) + 8 (r >> 2) + 4 h``, the unit accumulator register ``r`` of lane half
+      ``h`` holds (the fp32 branch of :func:`pack_mlp_weights` permutes the same way);
+    * ``c | g | ‖w‖²`` as ``[h][r]`` in that unit order. Padded units: ``‖w‖² = +inf`` (activation 0),
+      ``g = 1``, zero centre and zero output weights."""
+    H, n_in = Wc.shape
+    tiles = -(-H // 32)
+    W32 = np.zeros((tiles * 32, kp), np.float32)
+    W32[:H, :n_in] = Wc
+    Vp = np.zeros((32, tiles * 32), np.float32)
+    Vp[:V.shape[0], :H] = V
+    cp, gp = np.zeros(tiles * 32, np.float32), np.ones(tiles * 32, np.float32)
+    cp[:H], gp[:H] = c, g
+    wn = np.full(tiles * 32, np.inf, np.float32)
+    wn[:H] = (W32[:H].astype(np.float64) ** 2).sum(1)  # of the centres as stored: the expansion is exact for them
+    lane = np.arange(64)
+    m, h = lane & 31, lane >> 5
+    e = np.arange(4)
+    q = np.arange(kp // 8)
+    r = np.arange(16)
+    unit = (r[None, :] & 3) + 8 * (r[None, :] >> 2) + 4 * np.arange(2)[:, None]  # [h, r]
+    out = np.zeros((tiles, kp * 32 + RBF_TAIL), np.float32)
+    for t in range(tiles):
+        kk = 8 * q[:, None, None] + 4 * h[None, :, None] + e[None, None, :]  # [q, lane, e]
+        out[t, :kp * 32] = W32[32 * t + m[None, :, None], kk].reshape(-1)
+        uu = 32 * t + unit[h[None, :, None], 4 * np.arange(4)[:, None, None] + e[None, None, :]]  # [r4, lane, e]
+        out[t, kp * 32: kp * 32 + 1024] = Vp[m[None, :, None], uu].reshape(-1)
+        tail = kp * 32 + 1024
+        for i, arr in enumerate((cp, gp, wn)):
+            out[t, tail + 32 * i: tail + 32 * i + 32] = arr[32 * t + unit].reshape(-1)
+    return out
+
+
+class RbfPlan(MlpPlan):
+    """Radial-basis-function NeuralNetwork — a ``radialBasis`` hidden layer (optionally softmax /
+    simplemax normalised) and one dense output layer — on ``rbf_kernel`` (``ops/csrc/rbf.hip``):
+    the distances by expansion as an exact-fp32 MFMA product, the activation on its accumulators
+    and the output layer as a second product chained on those registers, one pass per row tile.
+    Inputs, outputs and the target decode are :class:`MlpPlan`'s. Parity: the oracle's
+    ``models/neural.py::NeuralEvaluator.forward``."""
+
+    kind = "rbf"
+    supports_direct = True
+    _STATE = DevicePlan._STATE + ("in_scale", "in_shift", "in_missing", "in_index", "n_in", "out_a", "out_b",
+                                  "final_norm", "n_out", "table", "is_classification", "target_stage", "panels",
+                                  "out_bias", "kp", "n_tiles", "hidden_norm", "out_act", "out_thr", "a_max",
+                                  "contiguous")
+
+    def __init__(self, compiled, device):
+        DevicePlan.__init__(self, compiled, device)
+        ev: NeuralEvaluator = compiled.evaluator
+        (_, out_layer), index = self._io(compiled, ev)
+        rbf = self._rbf
+        centers = rbf["centers"]
+        H = centers.shape[0]
+        if self.n_in > RBF_KPS[-1]:
+            raise NotLowerable(f"more than {RBF_KPS[-1]} inputs (RBF kernel)")
+        if self.n_in < 1 or H < 1:
+            raise NotLowerable("an RBF network needs at least one input and one hidden unit")
+        if H > RBF_HMAX:
+            raise NotLowerable(f"more than {RBF_HMAX} radialBasis units (RBF kernel)")
+        if self.n_out > 32:
+            raise NotLowerable("more than 32 output neurons (RBF kernel)")
+        self.hidden_norm = _HIDDEN_NORMS.get(rbf["normalization"])
+        if self.hidden_norm is None:
+            raise NotLowerable(f"hidden normalisation {rbf['normalization']!r}")
+        fan_in = rbf["fan_in"]
+        c = fan_in * np.log(rbf["altitude"])
+        self.a_max = float(np.exp(c.max()))
+        if not self.a_max <= RBF_AMAX:
+            raise NotLowerable(f"A_max = max altitude^fanIn = {self.a_max:.6g} > {RBF_AMAX:g} (RBF kernel)")
+        g = 1.0 / (2.0 * rbf["width"] ** 2)
+        # the centres' centroid moves into the input stage (exact in real arithmetic): both squared
+        # norms of the expansion shrink, and so does its cancellation
+        mu = centers.mean(axis=0)
+        self.in_shift = self._t((self.in_shift.cpu().numpy().astype(np.float64) - mu).astype(np.float32))
+        self.in_missing = self._t((self.in_missing.cpu().numpy().astype(np.float64) - mu).astype(np.float32))
+        W, b, act, thr, _ = out_layer
+        self.kp = next(k for k in RBF_KPS if self.n_in <= k)
+        pan = pack_rbf_panels(centers - mu, c, g, W.T, self.kp)
+        self.n_tiles = int(pan.shape[0])
+        self.panels = self._t(pan.reshape(-1))
+        bias = np.zeros(32, np.float32)
+        bias[:self.n_out] = b
+        self.out_bias = self._t(bias)
+        self.out_act, self.out_thr = ACT_CODES[act], float(thr)
+        self.contiguous = 1 if index == list(range(len(index))) else 0
+
+    def _layers(self, ev):
+        self._rbf = rbf = ev.rbf_layers()
+        act = rbf["output"][2]
+        if act not in ACT_CODES:
+            raise NotLowerable(f"output activation {act!r}")
+        return [None, rbf["output"]]
+
+    def launch(self, X, score, valid, stream=None, probs=None, score2=None, valid2=None) -> None:
+        import ctypes
+
+        from ..ops._lib import RbfArgs, check, ptr, stream_handle
+
+        a = RbfArgs()
+        a.X = X.data_ptr()
+        a.n_rows, a.n_feat, a.ldx, a.n_in = X.shape[0], X.shape[1], X.stride(0), self.n_in
+        a.in_scale, a.in_shift, a.in_missing = ptr(self.in_scale), ptr(self.in_shift), ptr(self.in_missing)
+        a.in_index, a.panels, a.out_bias = ptr(self.in_index), ptr(self.panels), ptr(self.out_bias)
+        a.kp, a.n_tiles, a.hidden_norm, a.out_act = self.kp, self.n_tiles, self.hidden_norm, self.out_act
+        a.out_thr, a.a_max, a.final_norm, a.n_out = self.out_thr, self.a_max, self.final_norm, self.n_out
+        a.classification = 1 if self.is_classification else 0
+        # vector row loads: identity input map over 16-byte aligned rows
+        a.contiguous = 1 if self.contiguous and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0 else 0
+        a.epi = _epilogue(mode=EPI_AFFINE, a=self.out_a, b=self.out_b, table=self.table, tgt=self.target_stage)
+        a.epi.score2, a.epi.valid2 = _addr(score2), _addr(valid2)
+        a.score, a.valid, a.probs = _addr(score), _addr(valid), ptr(probs)
+        check(self.lib.pmml_rbf_launch(stream_handle(stream), ctypes.byref(a)), "rbf kernel")
 
 
 _TORCH_ACT = {

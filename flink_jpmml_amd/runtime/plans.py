@@ -2306,6 +2306,10 @@ def compile_plan(compiled, device, **opts) -> DevicePlan:
             raise ValueError("mlp_impl must be auto, fused, wide or gemm")
 
         def build(c):
+            if ev.nn.layers and ev._layer_params(ev.nn.layers[0])[0] == "radialBasis":
+                from .nn_plans import RbfPlan  # a distance layer, not a dense one: its own kernel
+
+                return RbfPlan(c, device)
             if impl == "gemm":
                 return GemmMlpPlan(c, device, precision=prec)
             if impl == "wide":
