@@ -53,7 +53,9 @@ class _TreeGen:
         my = self.nid()
         split = depth < self.depth and (force_split or self.rng.random() < self.p_split)
         if not split:
-            out.write(f'{indent}<Node id="{my}" score="{leaf_fn()}">{pred}</Node>\n')
+            leaf = leaf_fn()  # the score, or (score, child elements of the leaf)
+            score, body = leaf if isinstance(leaf, tuple) else (leaf, "")
+            out.write(f'{indent}<Node id="{my}" score="{score}">{pred}{body}</Node>\n')
             return
         f = int(self.rng.integers(self.F))
         t = _fnum(self.thr[f, int(self.rng.integers(self.thr.shape[1]))])
@@ -217,9 +219,17 @@ def gbdt_pmml(n_trees: int = 1000, depth: int = 6, n_features: int = 32, seed: i
 
 
 def random_forest_pmml(n_trees: int = 500, depth: int = 8, n_features: int = 32, n_classes: int = 3,
-                       seed: int = 0, p_split: float = 0.85, missing_strategy: str = "defaultChild") -> str:
+                       seed: int = 0, p_split: float = 0.85, missing_strategy: str = "defaultChild",
+                       method: str = "majorityVote", distributions: bool = False) -> str:
     """scikit-learn-style majority-vote random forest (classification trees). ``missing_strategy``
-    ``"nullPrediction"`` is what sklearn2pmml exports: a missing split value voids the tree."""
+    ``"nullPrediction"`` is what sklearn2pmml exports: a missing split value voids the tree.
+    ``method``: ``majorityVote`` | ``weightedMajorityVote`` | ``average`` | ``weightedAverage`` (the
+    weighted ones draw each segment's weight from {0.5, 1, 2}). ``distributions``: every leaf carries
+    ``ScoreDistribution`` record counts of up to three classes that sum to 64 (leaf probabilities are
+    multiples of 1/64) and scores its first largest class. The extra random numbers are drawn only
+    when an option is set: the default document does not change."""
+    if method not in ("majorityVote", "weightedMajorityVote", "average", "weightedAverage"):
+        raise ValueError(f"method {method!r}")
     rng = np.random.default_rng(seed)
     thresholds = np.sort(rng.standard_normal((n_features, 64)).astype(np.float32), axis=1)
     cats = [str(c) for c in range(n_classes)]
@@ -228,14 +238,25 @@ def random_forest_pmml(n_trees: int = 500, depth: int = 8, n_features: int = 32,
     _data_dictionary(out, n_features, "y", "integer", cats)
     out.write(' <MiningModel functionName="classification" algorithmName="sklearn RandomForest">\n')
     _mining_schema(out, n_features, "y", "  ")
-    out.write('  <Segmentation multipleModelMethod="majorityVote">\n')
+    out.write(f'  <Segmentation multipleModelMethod="{method}">\n')
+
+    def leaf():
+        if not distributions:
+            return cats[int(rng.integers(n_classes))]
+        cls = np.sort(rng.choice(n_classes, size=min(3, n_classes), replace=False))
+        cuts = np.sort(rng.choice(np.arange(1, 64), size=len(cls) - 1, replace=False))
+        counts = np.diff(np.concatenate([[0], cuts, [64]]))
+        body = "".join(f'<ScoreDistribution value="{cats[c]}" recordCount="{int(n)}"/>' for c, n in zip(cls, counts))
+        return cats[int(cls[int(np.argmax(counts))])], body
+
     for t in range(n_trees):
         g = _TreeGen(rng, n_features, depth, p_split, thresholds)
-        out.write(f'   <Segment id="{t + 1}"><True/>\n')
+        weight = f' weight="{float(rng.choice([0.5, 1.0, 2.0]))}"' if method.startswith("weighted") else ""
+        out.write(f'   <Segment id="{t + 1}"{weight}><True/>\n')
         out.write(f'    <TreeModel functionName="classification" missingValueStrategy="{missing_strategy}" '
                   'splitCharacteristic="binarySplit">\n')
         _mining_schema(out, n_features, "y", "     ")
-        g.write(out, 0, "<True/>", lambda: cats[int(rng.integers(n_classes))], "     ", force_split=True)
+        g.write(out, 0, "<True/>", leaf, "     ", force_split=True)
         out.write('    </TreeModel>\n   </Segment>\n')
     out.write('  </Segmentation>\n </MiningModel>\n</PMML>\n')
     return out.getvalue()

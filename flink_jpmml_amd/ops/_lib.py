@@ -148,6 +148,15 @@ class TreeArgs(ctypes.Structure):
                 ("leaf_onehot", c_int)]
 
 
+class ClassTreeArgs(ctypes.Structure):
+    """tree_classes.hip ClassTreeArgs: a 17 to 256 class ensemble's nodes, leaves and the rows to score."""
+    _fields_ = [("X", c_void_p), ("n_rows", c_int), ("n_feat", c_int), ("ldx", c_int), ("n_stage", c_int),
+                ("prep", c_void_p), ("row_valid_in", c_void_p), ("feat_map", c_void_p), ("nodes", c_void_p),
+                ("roots", c_void_p), ("leaves", c_void_p), ("acc_init", c_void_p), ("n_trees", c_int), ("C", c_int),
+                ("Cp", c_int), ("dense", c_int), ("epi", Epilogue), ("score", c_void_p), ("valid", c_void_p),
+                ("probs", c_void_p)]
+
+
 class TextParseArgs(ctypes.Structure):
     _fields_ = [("buf", c_void_p), ("n_bytes", ctypes.c_longlong), ("starts", c_void_p), ("n_rows", c_int),
                 ("n_cols", c_int), ("colmap", c_void_p), ("F", c_int), ("delim", ctypes.c_char), ("n_missing", c_int),
@@ -343,6 +352,7 @@ _ABI = {
     "pmml_tree_grouped_args_size": GroupedTreeArgs,
     "pmml_tree_lds_args_size": LdsTreeArgs,
     "pmml_tree_hybrid_args_size": HybridArgs,
+    "pmml_tree_classes_args_size": ClassTreeArgs,
     "pmml_cluster_args_size": ClusterArgs,
     "pmml_knn_args_size": KnnArgs,
     "pmml_gemm_args_size": GemmArgs,
@@ -476,6 +486,8 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
         lib.pmml_tree_lds_launch.restype = c_int
         lib.pmml_tree_lds_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
         lib.pmml_tree_lds_bytes.restype = ctypes.c_longlong
+        lib.pmml_tree_classes_launch.argtypes = [c_void_p, ctypes.POINTER(ClassTreeArgs)]
+        lib.pmml_tree_classes_launch.restype = c_int
         lib.pmml_csr_expand.argtypes = [c_void_p, ctypes.POINTER(CsrExpandArgs)]
         lib.pmml_csr_expand.restype = c_int
         lib.pmml_csr_expand_rows.argtypes = [c_int]

@@ -343,6 +343,8 @@ class DevicePlan:
             from .derive import DerivedPlan as cls
         if cls is None and meta["__class__"] == "SegmentedPlan":
             from .segmented import SegmentedPlan as cls
+        if cls is None and meta["__class__"] == "ClassForestPlan":
+            from .class_forest import ClassForestPlan as cls
         if cls is None and meta["__class__"] == "SvmGemmPlan":
             from .nn_plans import SvmGemmPlan as cls
         if cls is None:
@@ -974,7 +976,12 @@ class NotBinaryForm(NotLowerable):
     """A tree is not in binary-split form: only the GENERAL (predicate-VM) layout can score it."""
 
 
-def ensemble_spec(compiled, lower=lower_binary_tree) -> EnsembleSpec:
+class ClassSlotLimit(NotLowerable):
+    """More class slots than TreePlan's kernels accumulate (nothing else is wrong with the model:
+    compile_plan moves on to the class-tile kernel, runtime/class_forest.py)."""
+
+
+def ensemble_spec(compiled, lower=lower_binary_tree, max_chain_classes: int = 16) -> EnsembleSpec:
     ev = compiled.evaluator
     field_index = getattr(compiled, "field_index", None) or {f: i for i, f in enumerate(compiled.active_fields)}
     try:
@@ -986,7 +993,7 @@ def ensemble_spec(compiled, lower=lower_binary_tree) -> EnsembleSpec:
                 epi["tgt"] = post
             return EnsembleSpec(trees, w, 1, 1, epi, None)
         if isinstance(ev, MiningEvaluator) and ev.mm.multiple_model_method == "modelChain":
-            return _chain_spec(compiled, ev, field_index, lower)
+            return _chain_spec(compiled, ev, field_index, lower, max_chain_classes)
         if isinstance(ev, MiningEvaluator) and ev.kind == "classification":
             return _classification_spec(ev, field_index, lower)
         if isinstance(ev, TreeEvaluator) and ev.kind == "classification":
@@ -1033,7 +1040,8 @@ def _classification_spec(ev: MiningEvaluator, field_index, lower=lower_binary_tr
     return EnsembleSpec(trees, weights, C, C, epi, cats)
 
 
-def _chain_spec(compiled, ev: MiningEvaluator, field_index, lower=lower_binary_tree) -> EnsembleSpec:
+def _chain_spec(compiled, ev: MiningEvaluator, field_index, lower=lower_binary_tree,
+                max_classes: int = 16) -> EnsembleSpec:
     """modelChain [regression tree ensemble(s) -> classification RegressionModel on their outputs]
     fused into one kernel + epilogue: the XGBoost / LightGBM binary export (one ensemble + logistic
     calibrator) and the K-class export (K ensembles, one per class, + softmax RegressionModel)."""
@@ -1072,8 +1080,9 @@ def _chain_spec(compiled, ev: MiningEvaluator, field_index, lower=lower_binary_t
     if norm != "softmax":
         raise NotLowerable(f"K-class chain normalizationMethod {norm!r} is host-only (softmax only)")
     K = len(rm.tables)
-    if K < 2 or K > 16:
-        raise NotLowerable(f"K-class chains with {K} classes are host-only (2..16)")
+    if K < 2 or K > max_classes:
+        raise (ClassSlotLimit if K >= 2 else NotLowerable)(
+            f"K-class chains with {K} classes are host-only (2..{max_classes})")
     trees, weights, slots, init = [], [], [], []
     for k, tab in enumerate(rm.tables):
         if tab.categorical or tab.terms or len(tab.numeric) > 1:
@@ -1587,7 +1596,7 @@ class TreePlan(DevicePlan):
                 spec, layout = self._general_spec(compiled), "general"
         self.full_epi, self.labels = dict(spec.epi), spec.labels
         if spec.C > 16:
-            raise NotLowerable(f"{spec.C} class slots: the tree kernels accumulate at most 16")
+            raise ClassSlotLimit(f"{spec.C} class slots: the tree kernels accumulate at most 16")
         if tree_shard is not None:
             if layout == "general":
                 raise NotLowerable("tree sharding needs the binary (perfect / pointer) layouts")
@@ -2282,8 +2291,15 @@ def compile_plan(compiled, device, **opts) -> DevicePlan:
         try:
             return TreePlan(compiled, device, precision="fp8" if policy == "fp8" else "fp32", **opts)
         except NotLowerable as e:
+            if isinstance(e, ClassSlotLimit):  # 17 to 256 classes: the class-tile kernel, where it applies
+                from .class_forest import ClassForestPlan
+
+                try:
+                    return ClassForestPlan(compiled, device, precision="fp8" if policy == "fp8" else "fp32", **opts)
+                except NotLowerable:
+                    pass
             if not isinstance(ev, MiningEvaluator):
-                raise
+                raise e
             return _segmented_plan(compiled, device, e, dict(opts, precision=policy))
     if isinstance(ev, RegressionEvaluator):
         try:
